@@ -16,14 +16,17 @@ parks every K cycles so exactly K cycles sit inside the timed region).
 OP: the operator is symmetric (dsaupd's contract), so by default the CSR is
 declared symmetric and the SpMV streams only its upper triangle
 (arpack_hip_csr_set_symmetric); the full-storage SpMV (bitwise SciPy's
-csr_matvec) runs the same K cycles beside it and is reported as `full_storage`.
+csr_matvec) runs the same K cycles beside it under --full (`full_storage`).
 
-Also reported: Lanczos steps/s (OP*x/s), time-to-converge at tol=1e-6, the
+A plain run sets up, warms up, times the K cycles and prints the line.  With
+--full it also runs and reports: the full-storage and other-accumulator
+companions, time-to-converge at tol=1e-6, the
 roofline of the dominant kernel (SpMV) from live hipEvent timing, and the
 reference CPU path (oracle/_ref: arpack-ng Fortran + OpenBLAS, OpenMP SpMV)
-timed on a bounded sample on the host cores.
+timed on a bounded sample on the host cores.  --dump-outputs DIR writes the
+timed solve's state after its last cycle as DIR/*.npy (dump_outputs below).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 Multi-GPU: launched by torch.distributed.run, one rank per GPU.
 """
 from __future__ import annotations
@@ -290,6 +293,46 @@ def comm_report(prof, D, dist, rank, ms_per_step):
                               "reading an N-rank line")
 
 
+DUMP_BLOCK = 256      # rows per sampled block
+DUMP_BLOCKS = 256     # blocks sampled: 65,536 rows x (ncv + 1) columns, 16 MB at ncv = 30
+
+
+def dump_rows(n, seed):
+    """The rows of resid / V that --dump-outputs writes: all of them while
+    n <= DUMP_BLOCK * DUMP_BLOCKS, else DUMP_BLOCKS blocks of DUMP_BLOCK
+    consecutive rows -- the first, the last (the ragged tail included) and a
+    draw of the others from default_rng(seed) -- as sorted (start, stop) pairs.
+    A function of (n, seed) only."""
+    if n <= DUMP_BLOCK * DUMP_BLOCKS:
+        return [(0, n)]
+    last = (n - 1) // DUMP_BLOCK
+    mid = np.random.default_rng(seed).choice(np.arange(1, last), DUMP_BLOCKS - 2, replace=False)
+    return [(int(b) * DUMP_BLOCK, min(n, (int(b) + 1) * DUMP_BLOCK))
+            for b in sorted([0, last] + mid.tolist())]
+
+
+def dump_outputs(d, s, seed):
+    """What a caller of the timed path holds after its last restart cycle, the
+    solve's dsaupd arguments, as d/<name>.npy in float64: iparam, workl (the
+    tridiagonal H, the Ritz values and their bounds, Q), and the rows
+    dump_rows(n, seed) of resid and of V's ncv columns (sample_rows names them)."""
+    os.makedirs(d, exist_ok=True)
+    blocks = dump_rows(s.n, seed)
+
+    def rows(buf, base):
+        if isinstance(buf, np.ndarray):
+            return np.concatenate([buf[base + a:base + b] for a, b in blocks])
+        return np.concatenate([buf.numpy(base + a, b - a) for a, b in blocks])
+
+    np.save(os.path.join(d, "iparam.npy"), s.iparam.astype(np.float64))
+    np.save(os.path.join(d, "workl.npy"), s.workl.astype(np.float64))
+    np.save(os.path.join(d, "sample_rows.npy"),
+            np.concatenate([np.arange(a, b) for a, b in blocks]).astype(np.float64))
+    np.save(os.path.join(d, "resid.npy"), rows(s.resid, 0).astype(np.float64))
+    np.save(os.path.join(d, "v.npy"),
+            np.stack([rows(s.v, j * s.ldv) for j in range(s.ncv)], axis=1).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -332,11 +375,26 @@ def main():
                     help="symmetric storage's transposed-term accumulator: fixed (the "
                          "fixed-point form, bitwise reproducible; default) or fp64 (LDS fp64 "
                          "atomics in schedule order); the other one runs beside as a companion")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything else the line can report, each "
+                         "from runs of its own: the full-storage and other-accumulator companions, "
+                         "the per-kernel profile (roofline, kernels, comm_profile), the steady "
+                         "cycles, time-to-converge and the CPU reference (the --no-* switches "
+                         "narrow it); without it those keys are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed solve holds after its last "
+                         "restart cycle (rank 0's rows) as DIR/<name>.npy, float64: iparam, workl, "
+                         "and a fixed seeded sample of the rows of resid and V")
     ap.add_argument("--deterministic", action="store_true",
                     help="deterministic mode (arpack_hip_set_deterministic): only fixed-order "
                          "SpMV forms (--storage sym: the fixed-point symmetric kernel "
                          "k_csr_ssell<..., DET = true>), so every solve is bitwise reproducible")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the K cycles, print the line
+        args.no_cpu_baseline = args.no_ttc = args.no_cpu_ttc = True
+        args.no_full_storage = args.no_profile = True
+        args.steady_cycles = 0
     if args.workload == "lap3d":
         args.n = args.m ** 3
         # the 7-pt Laplacian's top eigenvalues are clustered (multiplicities 3
@@ -516,6 +574,8 @@ def main():
                                  note="operator outside the fixed-point form")
         A.set_sym_accumulator(args.sym_acc)
     s, ido, elapsed, nopx, nsolves = timed_run()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, s, args.seed)
     # Per-kernel roofline: the next K cycles of the same solve with hipEvents on
     # every kernel's dispatch (start event on a span's first kernel, stop event
     # on its last: hipExtLaunchKernel), kept out of the timed region above; if that solve has

@@ -81,6 +81,48 @@ def test_newest_matching_summary_wins(tmp_path):
     assert bench.pmc_traffic({"k_csr_ssell"}, ns, str(tmp_path))[:2] == (3.0, "r06a_pmc.json")
 
 
+def test_dump_rows_sample():
+    """--dump-outputs' row sample: every row of a small operator; of a large
+    one 256 disjoint blocks of 256 rows, the first and the ragged last among
+    them, a function of (n, seed) alone."""
+    assert bench.dump_rows(1, 7) == [(0, 1)]
+    assert bench.dump_rows(65536, 7) == [(0, 65536)]
+    for n in (65537, 10_000_000, 9_999_999):
+        b = bench.dump_rows(n, 1234)
+        assert b == bench.dump_rows(n, 1234)
+        assert len(b) == 256 and b[0] == (0, 256) and b[-1][1] == n
+        assert 0 < b[-1][1] - b[-1][0] <= 256 and b[-1][0] % 256 == 0
+        assert all(a1 <= b0 for (_, a1), (b0, _) in zip(b, b[1:]))
+        assert all(hi - lo == 256 and lo % 256 == 0 for lo, hi in b[:-1])
+    assert bench.dump_rows(10_000_000, 1234) != bench.dump_rows(10_000_000, 1235)
+
+
+def test_dump_outputs_files(tmp_path):
+    """The files of --dump-outputs from a host-array solve state: float64, V as
+    (rows, ncv) read through its leading dimension, rows named by sample_rows."""
+    import numpy as np
+
+    class S:
+        n, ncv, ldv = 70_000, 3, 70_016
+        iparam = np.arange(11, dtype=np.int32)
+        workl = np.linspace(0.0, 1.0, 33)
+        resid = np.arange(70_000, dtype=np.float64)
+        v = np.arange(3 * 70_016, dtype=np.float64)
+
+    bench.dump_outputs(str(tmp_path / "o"), S, 5)
+    got = {f: np.load(tmp_path / "o" / f) for f in os.listdir(tmp_path / "o")}
+    assert sorted(got) == ["iparam.npy", "resid.npy", "sample_rows.npy", "v.npy", "workl.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    rows = got["sample_rows.npy"].astype(np.int64)
+    assert rows.size == 65_536 - 256 + 70_000 % 256 and rows[0] == 0 and rows[-1] == 69_999
+    assert np.array_equal(got["resid.npy"], S.resid[rows])
+    assert got["v.npy"].shape == (rows.size, 3)
+    for j in range(3):
+        assert np.array_equal(got["v.npy"][:, j], S.v[j * S.ldv + rows])
+    assert np.array_equal(got["iparam.npy"], np.arange(11.0))
+    assert np.array_equal(got["workl.npy"], S.workl)
+
+
 def _prof(steps, cycles, ar_ms, ar_n, h_ms, spmv_ms=10.0):
     p = {k: (0.0, 0.0, 0) for k in ("spmv", "cgs_dots", "update", "vq", "place", "finalize", "other",
                                     "allreduce", "halo")}

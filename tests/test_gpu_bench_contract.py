@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--rows", "300000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+SMALL = ["--full", "--rows", "300000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
          "--no-full-storage"]
 
 
@@ -70,7 +70,8 @@ def test_two_ranks_one_json_line():
     _comm_profile_ok(d, 2)
 
 
-LAP = ["--workload", "lap3d", "--lap-m", "100", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+LAP = ["--full", "--workload", "lap3d", "--lap-m", "100", "--steps", "2", "--warmup", "1",
+       "--no-cpu-baseline"]
 
 
 def test_lap3d_workload_line():
@@ -110,6 +111,41 @@ def test_plain_command_launches_n_ranks():
     d = _one_json(r.stdout)
     assert d["n_gpus"] == 2 and d["comm"]["ranks"] == 2
     assert [x["rank"] for x in d["comm"]["ranks_devices"]] == [0, 1]
+
+
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full) times its K cycles and nothing else -- the blocks
+    that take runs of their own are null -- and --dump-outputs writes the timed
+    solve's state as float64 .npy files, below 64 MB, bitwise equal between two
+    runs with the same arguments (the default fixed-point symmetric SpMV)."""
+    import numpy as np
+    dumps = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--rows", "300001",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines[:5]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["value"] > 0 and line["dtype"] == "f64"
+        assert abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-6
+        for k in ("time_to_converge", "full_storage", "accumulator_companion", "comm_profile"):
+            assert line[k] is None, k
+        assert "cpu_baseline" not in line and "steady_state" not in line
+        assert line["roofline"]["achieved"] is None
+        assert all(v["launches"] == 0 for v in line["kernels"].values())
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["iparam.npy", "resid.npy", "sample_rows.npy", "v.npy", "workl.npy"]
+    assert sum(x.nbytes for x in a.values()) < 64e6
+    rows = a["sample_rows.npy"]
+    assert rows[0] == 0 and rows[-1] == 300000 and a["v.npy"].shape == (rows.size, 30)
+    assert a["iparam.npy"][2] >= 1 and np.abs(a["resid.npy"]).max() > 0
+    for f in a:
+        assert a[f].dtype == np.float64 and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
 
 
 def test_more_gpus_than_present_fails():

@@ -122,8 +122,8 @@ def test_overlapped_distributed_spmv_same_solve(tmp_path):
     res = {}
     for ov in ("0", "1"):
         env = dict(os.environ, AHIP_DIST_OVERLAP=ov)
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist",
-                            "--rows", "400000", "--steps", "3", "--warmup", "1",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full",
+                            "--force-dist", "--rows", "400000", "--steps", "3", "--warmup", "1",
                             "--no-cpu-baseline", "--no-full-storage", "--steady-cycles", "0"],
                            env=env, capture_output=True, text=True, timeout=300, cwd=root)
         assert r.returncode == 0, r.stderr[-3000:]
