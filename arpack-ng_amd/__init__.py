@@ -83,6 +83,22 @@ def _declare(L):
     L.arpack_hip_csr_time.restype = C.c_double
     L.arpack_hip_csr_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.arpack_hip_csr_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.arpack_hip_csr_create_rect.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
+    L.arpack_hip_csr_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.arpack_hip_csr_kernel.argtypes = [C.c_void_p]
+    L.arpack_hip_csr_transpose_host.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 6
+    L.arpack_hip_dsvd_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int]
+    L.arpack_hip_dsvd_destroy.argtypes = [C.c_void_p]
+    L.arpack_hip_dsvd_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.arpack_hip_dsvd_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3 + \
+        [C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.arpack_hip_dsvd_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.arpack_hip_dsvd_time.restype = C.c_double
+    L.arpack_hip_dsaupd_svd.argtypes = [C.c_void_p] + L.dsaupd_c.argtypes
+    L.arpack_hip_dsvd_vectors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.arpack_hip_dsaupd_check.argtypes = [C.c_char_p, _I, C.c_char_p, _I, _I, _I, _I, _I, _I]
     L.arpack_hip_gen_laplace2d.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_double]
     L.arpack_hip_gen_laplace3d.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_double]
     L.arpack_hip_gen_laplace3d_rows.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_int64,
@@ -307,6 +323,11 @@ class CSR:
         nnz = C.c_int64()
         lib().arpack_hip_csr_info(self.h, C.byref(n), C.byref(nnz))
         self.n, self.nnz = n.value, nnz.value
+        nc = C.c_int64()
+        lib().arpack_hip_csr_shape(self.h, C.byref(n), C.byref(nc))
+        # (nrows, x length): a row block of a distributed operator reads an
+        # x longer than its rows too; only from_arrays(shape=) makes `rect`
+        self.shape = (n.value, nc.value)
         self._owner = owner
 
     def __del__(self):
@@ -318,16 +339,35 @@ class CSR:
             pass
 
     @classmethod
-    def from_arrays(cls, rowptr, col, val):
+    def from_arrays(cls, rowptr, col, val, shape=None):
+        """shape=(nrows, ncols): a rectangular operator
+        (arpack_hip_csr_create_rect; column indices checked against ncols) for
+        the product and svds; None: the square operator of the solvers."""
         rowptr = np.ascontiguousarray(rowptr, np.int64)
         col = np.ascontiguousarray(col, np.int32)
         val = np.ascontiguousarray(val, np.float64)
         h = C.c_void_p()
+        if shape is not None:
+            nr, nc = int(shape[0]), int(shape[1])
+            if nr != len(rowptr) - 1:
+                raise ValueError("shape[0] != len(rowptr) - 1")
+            rc = lib().arpack_hip_csr_create_rect(C.byref(h), nr, nc, len(col), rowptr.ctypes.data,
+                                                  col.ctypes.data, val.ctypes.data)
+            if rc != 0:
+                raise RuntimeError("arpack_hip_csr_create_rect failed (rc=%d)" % rc)
+            return cls(h.value)
         rc = lib().arpack_hip_csr_create(C.byref(h), len(rowptr) - 1, len(col), rowptr.ctypes.data,
                                          col.ctypes.data, val.ctypes.data)
         if rc != 0:
             raise RuntimeError("arpack_hip_csr_create failed")
         return cls(h.value)
+
+    @property
+    def kernel(self):
+        """The SpMV kernel the plan selected (arpack_hip_csr_kernel): 11 the
+        SELL-64 kernel (y bitwise a sequential CSR loop's), 1 / 2 CSR-stream,
+        0 vector."""
+        return lib().arpack_hip_csr_kernel(self.h)
 
     @classmethod
     def laplace2d(cls, m, scale=1.0):
@@ -418,8 +458,8 @@ class CSR:
         return ("full", "sym_fp64", "sym_fixed")[lib().arpack_hip_csr_sym_form(self.h)]
 
     def time_spmv(self, reps=20):
-        x = DeviceBuffer(self.n)
-        x.write(np.linspace(-1, 1, self.n))
+        x = DeviceBuffer(self.shape[1])
+        x.write(np.linspace(-1, 1, self.shape[1]))
         y = DeviceBuffer(self.n)
         return lib().arpack_hip_csr_time(self.h, x.ptr, y.ptr, reps)
 
@@ -533,6 +573,18 @@ class SymRci:
                                       _ip(self.iparam), _ip(self.ipntr), _ptr(self.workd),
                                       self.workl.ctypes.data, self.lworkl, _ip(self.info))
         self.tol = tol.value
+        return int(self.ido[0])
+
+    def aupd_svd(self, S: "SVDOp"):
+        """Whole loop on the GPU with OP = B'B, the normal operator S of a
+        rectangular matrix (arpack_hip_dsaupd_svd; n = S.k, mode 1)."""
+        lib().arpack_hip_dsaupd_svd(S.h, _ip(self.ido), self.bmat.encode(), self.n,
+                                    self.which.encode(), self.nev, self.tol, _ptr(self.resid),
+                                    self.ncv, _ptr(self.v), self.ldv, _ip(self.iparam),
+                                    _ip(self.ipntr), _ptr(self.workd), self.workl.ctypes.data,
+                                    self.lworkl, _ip(self.info))
+        if self.tol <= 0.0:  # the solve used eps (SRC/dsaupd.f:550); keep it for dseupd
+            self.tol = float(np.finfo(np.float64).eps / 2)
         return int(self.ido[0])
 
     def aupd_gen(self, G: "DGen"):
@@ -1174,6 +1226,158 @@ def eigs(op, n, nev=6, ncv=None, which="LM", tol=0.0, v0=None, mxiter=300, rvec=
     dr, di, z, nconv = s.eupd(rvec=rvec, sigmar=float(sigma) if shift else 0.0)
     d = dr + 1j * di
     return d, (_ns_vectors(dr, di, z, n, nconv) if rvec else None), res
+
+
+# ------------------------------------------------------------- truncated SVD
+def csr_transpose(rowptr, col, val, shape):
+    """Host transpose of an nrows x ncols CSR matrix
+    (arpack_hip_csr_transpose_host; no GPU needed): a stable counting sort, so
+    each row of the transpose keeps increasing source rows -- the arrays of
+    SciPy's A.T.tocsr() with sorted indices.  Returns (rowptr, col, val)."""
+    rowptr = np.ascontiguousarray(rowptr, np.int64)
+    col = np.ascontiguousarray(col, np.int32)
+    val = np.ascontiguousarray(val, np.float64)
+    nr, nc = int(shape[0]), int(shape[1])
+    if len(rowptr) != nr + 1 or len(col) != len(val) or (nr >= 0 and rowptr[-1] != len(col)):
+        raise ValueError("CSR arrays do not match the shape")
+    trp = np.zeros(max(nc, 0) + 1, np.int64)
+    tc = np.zeros(len(col), np.int32)
+    tv = np.zeros(len(col), np.float64)
+    rc = lib().arpack_hip_csr_transpose_host(nr, nc, rowptr.ctypes.data, col.ctypes.data,
+                                             val.ctypes.data, trp.ctypes.data, tc.ctypes.data,
+                                             tv.ctypes.data)
+    if rc != 0:
+        raise ValueError("arpack_hip_csr_transpose_host: bad shape or index (rc=%d)" % rc)
+    return trp, tc, tv
+
+
+_SVD_FORMS = {"auto": 0, "two_product": 1, "fused": 2}
+
+
+class SVDOp:
+    """The normal operator y = B'(B x) of a (rectangular) CSR matrix A on the
+    GPU (arpack_hip_dsvd_*): A is m x n, k = min(m, n), B the tall orientation.
+    form: "two_product" (w = B x, y = B' w: fixed order, bitwise reproducible,
+    any shape), "fused" (one pass over B with x and y in LDS, k <= fused_kmax;
+    reproducible to rounding, not bitwise) or "auto" (two-product when
+    k > fused_kmax or in deterministic mode).  One stream per object."""
+
+    def __init__(self, A: CSR, form="auto"):
+        if form not in _SVD_FORMS:
+            raise ValueError("form must be one of %s" % sorted(_SVD_FORMS))
+        h = C.c_void_p()
+        rc = lib().arpack_hip_dsvd_create(C.byref(h), A.h, _SVD_FORMS[form])
+        self.h = None
+        if rc != 0:  # -1 bad argument (form "fused" with k > fused_kmax), -2 HIP / plan failure
+            raise ArpackError("arpack_hip_dsvd_create", rc)
+        self.h, self.A = h, A  # (keeps the matrix alive)
+        i = self.info()
+        self.m, self.n, self.k, self.form = i["m"], i["n"], i["k"], i["form"]
+        self.fused_kmax = i["fused_kmax"]
+
+    def __del__(self):
+        try:
+            if self.h and _lib is not None:
+                _lib.arpack_hip_dsvd_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def info(self):
+        v = [C.c_int64() for _ in range(3)]
+        f, km = C.c_int(), C.c_int64()
+        lib().arpack_hip_dsvd_info(self.h, *[C.byref(x) for x in v], C.byref(f), C.byref(km))
+        return dict(m=v[0].value, n=v[1].value, k=v[2].value,
+                    form={1: "two_product", 2: "fused"}[f.value], fused_kmax=km.value)
+
+    def apply(self, x, y=None):
+        """y = B'(B x).  Device mode: x, y DeviceBuffers (or addresses) of k
+        doubles, y returned; a host vector x returns a host vector."""
+        if isinstance(x, np.ndarray):
+            xb, yb = DeviceBuffer.from_numpy(np.ascontiguousarray(x, np.float64)), DeviceBuffer(self.k)
+            self.apply(xb, yb)
+            return yb.numpy()
+        xp = x if isinstance(x, int) else _ptr(x)
+        yp = y if isinstance(y, int) else _ptr(y)
+        rc = lib().arpack_hip_dsvd_apply(self.h, xp, yp)
+        if rc != 0:
+            raise RuntimeError("arpack_hip_dsvd_apply failed (rc=%d)" % rc)
+        return y
+
+    def time(self, reps=20):
+        """Average device ms of one apply (arpack_hip_dsvd_time)."""
+        x = DeviceBuffer(self.k)
+        x.write(np.linspace(-1, 1, self.k))
+        y = DeviceBuffer(self.k)
+        ms = lib().arpack_hip_dsvd_time(self.h, x.ptr, y.ptr, int(reps))
+        if ms < 0:
+            raise RuntimeError("arpack_hip_dsvd_time failed")
+        return ms
+
+    def vectors(self, d, z, ldz=None):
+        """dsvd.f's post-processing (arpack_hip_dsvd_vectors) of the Ritz pairs
+        (d host, z a DeviceBuffer of k x len(d), ldz): returns (sigma, Uother
+        as a max(m, n) x len(d) host array, resid)."""
+        d = np.ascontiguousarray(d, np.float64)
+        nc, rows = len(d), max(self.m, self.n)
+        sig, res = np.zeros(nc), np.zeros(nc)
+        uo = DeviceBuffer(max(nc, 1) * rows)
+        rc = lib().arpack_hip_dsvd_vectors(self.h, nc, d.ctypes.data, _ptr(z), ldz or self.k,
+                                           sig.ctypes.data, uo.ptr, rows, res.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("arpack_hip_dsvd_vectors failed (rc=%d)" % rc)
+        return sig, uo.numpy()[:nc * rows].reshape(nc, rows).T, res
+
+
+def svds(A, k=6, ncv=None, tol=0.0, which="LM", v0=None, mxiter=300,
+         return_singular_vectors=True, form="auto"):
+    """Truncated SVD of a sparse m x n matrix on the GPU, the calling pattern of
+    EXAMPLES/SVD/dsvd.f (and SciPy's svds(solver="arpack")): dsaupd in mode 1 on
+    B'B (B the tall orientation of A, dimension min(m, n)) as a free run on the
+    device, dseupd, then sigma = sqrt(lambda) and the other side's vectors
+    B z / ||B z||.
+
+    A: a CSR (CSR.from_arrays(..., shape=(m, n))), or a SciPy sparse matrix,
+    which is uploaded after the arguments passed their checks.  which: "LM" or
+    "SM" (passed to dsaupd; "SM" is plain mode 1, no shift-invert).  form: see
+    SVDOp.  Returns (U, s, Vt, info): s ascending, as ARPACK returns the Ritz
+    values, U m x nconv, Vt nconv x n (None without vectors); info is eigsh's
+    dict plus `form` and `resid` (dsvd.f's ||B z - sigma u|| per triplet).  Bad
+    k / ncv raise ArpackError with dsaupd's info code."""
+    if which not in ("LM", "SM"):
+        raise ValueError('which must be "LM" or "SM"')
+    if form not in _SVD_FORMS:
+        raise ValueError("form must be one of %s" % sorted(_SVD_FORMS))
+    m, n = int(A.shape[0]), int(A.shape[1])
+    kd = min(m, n)
+    k = int(k)
+    ncv = int(ncv) if ncv else min(kd, max(2 * k + 1, 20))
+    # the engine's own argument checks, before anything touches the device
+    rc = lib().arpack_hip_dsaupd_check(b"I", kd, which.encode(), k, ncv, ncv * ncv + 8 * ncv, 1, 1,
+                                       int(mxiter))
+    if rc != 0:
+        raise ArpackError("dsaupd", rc)
+    if not isinstance(A, CSR):
+        S = A.tocsr()
+        S.sort_indices()
+        A = CSR.from_arrays(S.indptr, S.indices, S.data, shape=(m, n))
+    op = SVDOp(A, form)
+    s = SymRci(kd, k, ncv, which, tol, mxiter=mxiter, v0=v0, device=True)
+    s.aupd_svd(op)
+    if s.info[0] < 0:
+        raise ArpackError("dsaupd", int(s.info[0]))
+    res = dict(info=int(s.info[0]), iters=int(s.iparam[2]), nconv=int(s.iparam[4]),
+               nopx=int(s.iparam[8]), nrorth=int(s.iparam[10]), ritz=s.ritz, form=op.form)
+    d, z, nconv = s.eupd(rvec=return_singular_vectors)
+    sig = np.sqrt(np.maximum(d, 0.0))
+    if not return_singular_vectors:
+        return None, sig, None, res
+    sig, uo, resid = op.vectors(d, z, kd)
+    Z = z.numpy()[:nconv * kd].reshape(nconv, kd)  # row j = the short side's vector j
+    res["resid"] = resid
+    if m >= n:
+        return uo, sig, Z.copy(), res
+    return Z.T.copy(), sig, uo.T.copy(), res
 
 
 # ----------------------------------------------------------- multi-GPU (RCCL)

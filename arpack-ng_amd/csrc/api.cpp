@@ -18,6 +18,7 @@
 
 const ahip::dev::Csr* ahip_csr_view(const arpack_hip_csr* A);
 const ahip::DistOp* ahip_dist_view(const arpack_hip_dist* D);
+bool ahip_csr_is_rect(const arpack_hip_csr* A);
 
 namespace ahip {
 
@@ -137,8 +138,9 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
                      R* resid, int ncv, R* v, int ldv, int* iparam, int* ipntr, R* workd,
                      R* workl, int lworkl, int* info, const dev::Csr* csr, int max_cycles = -1,
                      const DistOp* dist = nullptr, bool ns = false, dev::DShift* shift = nullptr,
-                     dev::DGen* gen = nullptr) {
+                     dev::DGen* gen = nullptr, dev::DSvd* svd = nullptr) {
     constexpr bool kShadow = !std::is_same_v<R, double>;
+    if (svd) csr = ahip_csr_view(svd->B);  // truncated SVD free run: OP = B'B on the device
     if (dist) csr = dist->A;
     if (shift) csr = shift->A;  // mode 3 free run: OP = (A - sigma I)^{-1} on the device
     if (gen) csr = gen->A;      // modes 2-5, bmat = 'G': OP and B on the device
@@ -170,6 +172,8 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
                 (ns && mode != 2 && mode != 3 && !(gen->cshift && mode == 4)) ||
                 (!ns && gen->cshift))
                 ierr = (ierr ? ierr : -11);
+        } else if (svd) {  // mode 1, bmat = 'I', n = min(m, n)
+            if (ns || dist || mode != 1 || bmat[0] != 'I' || svd->k != n) ierr = (ierr ? ierr : -11);
         } else if (csr && ((shift ? mode != 3 || dist ||
                                         (ns && shift->method != dev::kDShiftBicgstab &&
                                          shift->method != dev::kDShiftTridiag)
@@ -245,6 +249,7 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
             S->csr = csr;
             S->shift = shift;
             S->gen = gen;
+            S->svd = svd;
         }
         if (dist) {
             S->dist = dist;
@@ -343,6 +348,18 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
             }
             continue;
         }
+        if (S->svd && (r.ido == -1 || r.ido == 1)) {
+            // the normal operator's kernels carry no finalize: launch the
+            // deferred one first, ahead of them in stream order
+            if constexpr (!kShadow) {
+                dev::flush_deferred_finalize(S->ws.defq, S->a.stream);
+                dev::prof_arm(dev::kProfSpmv, S->a.stream);
+                const int rc = dev::dsvd_apply(*S->svd, S->a.stream, S->op_x, S->op_y);
+                dev::prof_disarm(dev::kProfSpmv, dev::dsvd_bytes(*S->svd));
+                if (rc != 0) S->a.ck(hipErrorLaunchFailure);  // ends the solve: info = -9999
+            }
+            continue;
+        }
         if (S->free_run && (r.ido == -1 || r.ido == 1)) {
             // kernel-mode timing (the SpMV kernels' own execution, as rocprofv3 reports
             // it); a row-distributed SpMV also holds its halo exchange: marker mode
@@ -437,6 +454,15 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
 
 using namespace ahip;
 
+// a square-operator solver entry handed a rectangular CSR
+// (arpack_hip_csr_create_rect): the bad-argument return, before anything runs
+static bool refuse_rect(const arpack_hip_csr* A, int* ido, int* info) {
+    if (!ahip_csr_is_rect(A)) return false;
+    *info = -1;
+    *ido = 99;
+    return true;
+}
+
 extern "C" {
 
 void dsaupd_c(int* ido, char const* bmat, int n, char const* which, int nev, double tol,
@@ -500,6 +526,7 @@ void arpack_hip_dnaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* 
                                   char const* bmat, int n, char const* which, int nev, double* tol,
                                   double* resid, int ncv, double* v, int ldv, int* iparam,
                                   int* ipntr, double* workd, double* workl, int lworkl, int* info) {
+    if (refuse_rect(A, ido, info)) return;
     sym_aupd(ido, bmat, n, which, nev, tol, resid, ncv, v, ldv, iparam, ipntr, workd, workl, lworkl,
              info, ahip_csr_view(A), max_cycles, nullptr, true);
 }
@@ -515,6 +542,7 @@ void arpack_hip_dsaupd_csr(const arpack_hip_csr* A, int* ido, char const* bmat, 
                            char const* which, int nev, double tol, double* resid, int ncv,
                            double* v, int ldv, int* iparam, int* ipntr, double* workd,
                            double* workl, int lworkl, int* info) {
+    if (refuse_rect(A, ido, info)) return;
     sym_aupd(ido, bmat, n, which, nev, &tol, resid, ncv, v, ldv, iparam, ipntr, workd, workl,
              lworkl, info, ahip_csr_view(A));
 }
@@ -523,6 +551,7 @@ void arpack_hip_dsaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* 
                                   char const* bmat, int n, char const* which, int nev, double* tol,
                                   double* resid, int ncv, double* v, int ldv, int* iparam,
                                   int* ipntr, double* workd, double* workl, int lworkl, int* info) {
+    if (refuse_rect(A, ido, info)) return;
     sym_aupd(ido, bmat, n, which, nev, tol, resid, ncv, v, ldv, iparam, ipntr, workd, workl, lworkl,
              info, ahip_csr_view(A), max_cycles);
 }
@@ -624,7 +653,7 @@ void arpack_hip_dnaupd_gen(arpack_hip_dgen* D, int* ido, char const* bmat, int n
 
 int arpack_hip_dshift_create(arpack_hip_dshift** out, const arpack_hip_csr* A, double sigma,
                              double rtol, int maxit) {
-    if (!out || !A || !(rtol > 0.0) || maxit < 1) return -1;
+    if (!out || !A || ahip_csr_is_rect(A) || !(rtol > 0.0) || maxit < 1) return -1;
     auto* D = new arpack_hip_dshift;
     if (ahip::dev::dshift_create(D->S, ahip_csr_view(A), sigma, rtol, maxit) != 0) {
         delete D;
@@ -695,6 +724,99 @@ void arpack_hip_dnaupd_shift(arpack_hip_dshift* D, int* ido, char const* bmat, i
     }
     sym_aupd(ido, bmat, n, which, nev, tol, resid, ncv, v, ldv, iparam, ipntr, workd, workl, lworkl,
              info, nullptr, -1, nullptr, true, &D->S);
+}
+
+// ---- truncated SVD on the device (dsvd.f's calling pattern, dsvd.cpp) -------
+struct arpack_hip_dsvd {
+    ahip::dev::DSvd S;
+};
+
+int arpack_hip_dsvd_create(arpack_hip_dsvd** out, const arpack_hip_csr* A, int form) {
+    if (!out || !A || form < ahip::dev::kSvdAuto || form > ahip::dev::kSvdFused) return -1;
+    auto* D = new arpack_hip_dsvd;
+    const int rc = ahip::dev::dsvd_create(D->S, A, form);
+    if (rc != 0) {
+        delete D;
+        return rc;
+    }
+    *out = D;
+    return 0;
+}
+
+void arpack_hip_dsvd_destroy(arpack_hip_dsvd* D) {
+    if (!D) return;
+    ahip::dev::dsvd_destroy(D->S);
+    delete D;
+}
+
+int arpack_hip_dsvd_apply(arpack_hip_dsvd* D, const double* x, double* y) {
+    if (!D || !x || !y || x == y) return -1;
+    // x may come from the caller's own stream (as arpack_hip_csr_spmv)
+    if (hipDeviceSynchronize() != hipSuccess) return -2;
+    const int rc = ahip::dev::dsvd_apply(D->S, nullptr, x, y);
+    return rc == 0 && fault_filter(hipStreamSynchronize(nullptr)) == hipSuccess ? 0 : -2;
+}
+
+int arpack_hip_dsvd_info(const arpack_hip_dsvd* D, int64_t* m, int64_t* n, int64_t* k, int* form,
+                         int64_t* fused_kmax) {
+    if (!D) return -1;
+    if (m) *m = D->S.m;
+    if (n) *n = D->S.n;
+    if (k) *k = D->S.k;
+    if (form) *form = D->S.form;
+    if (fused_kmax) *fused_kmax = ahip::dev::kNormalKmax;
+    return 0;
+}
+
+double arpack_hip_dsvd_time(arpack_hip_dsvd* D, const double* x, double* y, int reps) {
+    if (!D || !x || !y || x == y || reps < 1) return -1.0;
+    hipEvent_t a, b;
+    if (hipEventCreate(&a) != hipSuccess) return -1.0;
+    if (hipEventCreate(&b) != hipSuccess) {
+        (void)hipEventDestroy(a);
+        return -1.0;
+    }
+    int rc = ahip::dev::dsvd_apply(D->S, nullptr, x, y);  // warm
+    (void)hipEventRecord(a, nullptr);
+    for (int r = 0; r < reps && rc == 0; ++r) rc = ahip::dev::dsvd_apply(D->S, nullptr, x, y);
+    (void)hipEventRecord(b, nullptr);
+    float ms = 0.f;
+    if (hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) rc = -2;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return rc == 0 ? (double)ms / reps : -1.0;
+}
+
+void arpack_hip_dsaupd_svd(arpack_hip_dsvd* D, int* ido, char const* bmat, int n, char const* which,
+                           int nev, double tol, double* resid, int ncv, double* v, int ldv,
+                           int* iparam, int* ipntr, double* workd, double* workl, int lworkl,
+                           int* info) {
+    if (!D) {
+        *info = -9999;
+        *ido = 99;
+        return;
+    }
+    sym_aupd(ido, bmat, n, which, nev, &tol, resid, ncv, v, ldv, iparam, ipntr, workd, workl,
+             lworkl, info, nullptr, -1, nullptr, false, nullptr, nullptr, &D->S);
+}
+
+int arpack_hip_dsvd_vectors(arpack_hip_dsvd* D, int nconv, const double* d, const double* Z,
+                            int64_t ldz, double* sigma_out, double* Uother, int64_t ldu,
+                            double* resid_out) {
+    if (!D) return -1;
+    return ahip::dev::dsvd_vectors(D->S, nconv, d, Z, ldz, sigma_out, Uother, ldu, resid_out);
+}
+
+int arpack_hip_dsaupd_check(char const* bmat, int n, char const* which, int nev, int ncv,
+                            int lworkl, int mode, int ishift, int mxiter) {
+    if (!bmat || !which) return -9999;
+    return sym_check(bmat[0], n, la::parse_which(which), nev, ncv, lworkl, mode, ishift, mxiter);
+}
+
+int arpack_hip_csr_transpose_host(int64_t nrows, int64_t ncols, const int64_t* rowptr,
+                                  const int32_t* col, const double* val, int64_t* trowptr,
+                                  int32_t* tcol, double* tval) {
+    return ahip::dev::csr_transpose_host(nrows, ncols, rowptr, col, val, trowptr, tcol, tval);
 }
 
 // Row-block distributed solve (PARPACK's pdsaupd decomposition, n = LOCAL rows):

@@ -316,6 +316,62 @@ int arpack_hip_csr_create(arpack_hip_csr** out, int64_t n, int64_t nnz, const in
     return finish(out, n, n, nnz, rp, c, v);
 }
 
+int arpack_hip_csr_create_rect(arpack_hip_csr** out, int64_t nrows, int64_t ncols, int64_t nnz,
+                               const int64_t* rowptr, const int32_t* col, const double* val) {
+    if (!out || nrows < 1 || ncols < 1 || ncols > (int64_t)INT32_MAX || nnz < 0 || !rowptr ||
+        (nnz > 0 && (!col || !val)))
+        return -1;
+    // the shape is the caller's word: every index is checked against it before a
+    // kernel gathers x with it (host copies; the pointers may be device ones)
+    std::vector<int64_t> hrp((size_t)nrows + 1);
+    std::vector<int32_t> hc((size_t)nnz);
+    if (hipMemcpy(hrp.data(), rowptr, sizeof(int64_t) * (nrows + 1), hipMemcpyDefault) != hipSuccess ||
+        (nnz > 0 && hipMemcpy(hc.data(), col, sizeof(int32_t) * nnz, hipMemcpyDefault) != hipSuccess))
+        return -1;
+    if (hrp[0] != 0 || hrp[nrows] != nnz) return -1;
+    for (int64_t i = 0; i < nrows; ++i)
+        if (hrp[i + 1] < hrp[i]) return -1;
+    for (int64_t k = 0; k < nnz; ++k)
+        if (hc[k] < 0 || hc[k] >= ncols) return -1;
+    int64_t* rp = nullptr;
+    int32_t* c = nullptr;
+    double* v = nullptr;
+    bool ok = hipMalloc(&rp, sizeof(int64_t) * (nrows + 1)) == hipSuccess &&
+              hipMalloc(&c, sizeof(int32_t) * (nnz > 0 ? nnz : 1)) == hipSuccess &&
+              hipMalloc(&v, sizeof(double) * (nnz > 0 ? nnz : 1)) == hipSuccess &&
+              hipMemcpy(rp, hrp.data(), sizeof(int64_t) * (nrows + 1), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && nnz > 0)
+        ok = hipMemcpy(c, hc.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(v, val, sizeof(double) * nnz, hipMemcpyDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipFree(rp);
+        (void)hipFree(c);
+        (void)hipFree(v);
+        return -1;
+    }
+    // the planners of the square operator with ncols passed through: LDS x
+    // windows + SELL-64 where every row's columns fit a window, else the
+    // CSR-stream or the vector kernel
+    const int rc = finish(out, nrows, ncols, nnz, rp, c, v);
+    if (rc == 0) (*out)->rect = nrows != ncols;
+    return rc;
+}
+
+int arpack_hip_csr_shape(const arpack_hip_csr* A, int64_t* nrows, int64_t* ncols) {
+    if (!A) return -1;
+    if (nrows) *nrows = A->A.n;
+    if (ncols) *ncols = A->ncols;
+    return 0;
+}
+
+int arpack_hip_csr_kernel(const arpack_hip_csr* A) {
+    if (!A) return -1;
+    const ahip::dev::Csr& M = A->A;
+    if (ahip::dev::csr_sym_det_fallback(M))
+        return M.s_val ? ahip::dev::kCsrSell : (M.rblk ? ahip::dev::kCsrStream : ahip::dev::kCsrVector);
+    return M.kernel;
+}
+
 void arpack_hip_csr_destroy(arpack_hip_csr* A) {
     if (!A) return;
     ahip_dist_detach_csr(A->dist);
@@ -369,6 +425,7 @@ static void csr_full_storage(arpack_hip_csr* A) {
 }
 
 int arpack_hip_csr_set_symmetric(arpack_hip_csr* A, int on) {
+    if (A->rect) return -1;  // symmetric storage is a square operator's
     // one rank's block of a distributed operator: the symmetric SpMV changes the
     // exchange pattern (hi-only halo + forward spill), so the switch -- either
     // way -- is collective, and every rank falls back to full storage if any
@@ -569,6 +626,8 @@ int arpack_hip_gen_banded_sym(arpack_hip_csr** out, int64_t n, int64_t r0, int64
 }  // extern "C"
 
 const ahip::dev::Csr* ahip_csr_view(const arpack_hip_csr* A) { return &A->A; }
+bool ahip_csr_is_rect(const arpack_hip_csr* A) { return A && A->rect; }
+int64_t ahip_csr_ncols(const arpack_hip_csr* A) { return A->ncols; }
 
 // ------------------------------------------------------------ remap helpers --
 namespace {

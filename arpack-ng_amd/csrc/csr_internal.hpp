@@ -28,8 +28,17 @@ struct arpack_hip_csr {
     // distributed operator, so a storage-mode switch must be agreed by all ranks
     // (cleared by arpack_hip_dist_destroy)
     arpack_hip_dist* dist = nullptr;
+    // made by arpack_hip_csr_create_rect with nrows != ncols: serves the product
+    // (x of ncols, y of A.n) and the SVD's normal operator only; symmetric
+    // storage, the distribution and every square-operator solver entry refuse it
+    bool rect = false;
 };
 
+
+// a rectangular operator (arpack_hip_csr_create_rect, nrows != ncols)
+bool ahip_csr_is_rect(const arpack_hip_csr* A);
+// length of the x vector A's product reads
+int64_t ahip_csr_ncols(const arpack_hip_csr* A);
 
 // the live communicator of A's distribution (nullptr if A is not distributed
 // or, with *stale = true, if that communicator has been destroyed)

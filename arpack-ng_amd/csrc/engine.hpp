@@ -14,6 +14,7 @@
 #include "dist.hpp"
 #include "dgen.hpp"
 #include "dshift.hpp"
+#include "dsvd.hpp"
 #include "rci.hpp"
 
 namespace ahip {
@@ -135,6 +136,10 @@ public:
     // generalized modes free run (arpack_hip_dsaupd_gen): OP*x and B*x on the
     // device (csr = gen->A)
     dev::DGen* gen = nullptr;
+    // truncated SVD free run (arpack_hip_dsaupd_svd): OP = B'B on the device
+    // (csr = the tall orientation B, for its size only); the chained / folded
+    // steps and the finalize-carrying SpMV stay off for it
+    dev::DSvd* svd = nullptr;
 
     // nonsymmetric Arnoldi (dnaupd): full upper-Hessenberg H (ld ncv)
     bool arnoldi = false;

@@ -288,6 +288,89 @@ void arpack_hip_dnaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* 
                                   int* iparam, int* ipntr, double* workd, double* workl,
                                   int lworkl, int* info);
 
+/* ---- truncated SVD on the device (EXAMPLES/SVD/dsvd.f, SciPy's svds) ---------- *
+ * A rectangular CSR matrix, nrows x ncols (the pointer rules of
+ * arpack_hip_csr_create).  arpack_hip_csr_spmv reads x of ncols and writes y of
+ * nrows entries; arpack_hip_csr_info reports nrows.  0; -1 for a bad shape
+ * (nrows or ncols < 1, nnz < 0, ncols > 2^31 - 1), a column index outside
+ * [0, ncols) or arrays that could not be placed in HBM; -2 if the SpMV plan
+ * analysis failed.  With nrows != ncols the operator serves the product and
+ * arpack_hip_dsvd_create only: arpack_hip_csr_set_symmetric (and set_kernel 12),
+ * arpack_hip_dist_create, arpack_hip_dshift_create and arpack_hip_dgen_create
+ * return -1 for it, and the square-operator solver entries
+ * (arpack_hip_dsaupd_csr, _csr_cycles, arpack_hip_dnaupd_csr_cycles) end with
+ * ido = 99, info = -1. */
+int arpack_hip_csr_create_rect(arpack_hip_csr** A, int64_t nrows, int64_t ncols, int64_t nnz,
+                               const int64_t* rowptr, const int32_t* col, const double* val);
+/* nrows and ncols of A. */
+int arpack_hip_csr_shape(const arpack_hip_csr* A, int64_t* nrows, int64_t* ncols);
+/* The SpMV kernel A's plan selected (the numbering of arpack_hip_csr_set_kernel;
+ * 11 = SELL-64 slices over LDS x windows, whose y is bitwise a sequential CSR
+ * loop's; 1 / 2 CSR-stream and 0 vector sum a row in lane groups). */
+int arpack_hip_csr_kernel(const arpack_hip_csr* A);
+/* Host-only transpose of an nrows x ncols CSR matrix (no GPU needed): a stable
+ * counting sort, so within each row of the transpose the entries keep
+ * increasing source-row order (sorted column indices, the layout of SciPy's
+ * A.T.tocsr()).  trowptr int64[ncols + 1], tcol int32[nnz], tval f64[nnz] are
+ * the caller's.  0; -1 on a bad shape, rowptr or column index. */
+int arpack_hip_csr_transpose_host(int64_t nrows, int64_t ncols, const int64_t* rowptr,
+                                  const int32_t* col, const double* val, int64_t* trowptr,
+                                  int32_t* tcol, double* tval);
+
+/* The normal operator of A's truncated SVD.  A is m x n (square allowed),
+ * k = min(m, n), B the tall orientation (B = A if m >= n, else A'); the object
+ * applies y = B'(B x) on R^k.  form: 0 auto, 1 two-product, 2 fused.
+ *   two-product: w = B x, y = B' w with the stored transpose and the
+ *     full-storage SpMV kernels.  Fixed summation order: bitwise reproducible.
+ *     Any shape.  Streams the matrix twice (2 x 12 B an entry).
+ *   fused: one pass over B (10 B a stored entry): every workgroup keeps x and
+ *     a y accumulator of k doubles each in LDS, forms w_i for its rows and adds
+ *     a_ij w_i into y there, writes its k-length partial to scratch, and a
+ *     second kernel sums the partials in block order.  Serves k <= fused_kmax =
+ *     10240 (2 x 8 B x k = the 160 KB of LDS).  The LDS adds run in
+ *     wave-schedule order: y is reproducible to rounding, not bitwise.
+ *   auto: two-product when k > fused_kmax or in deterministic mode
+ *     (arpack_hip_set_deterministic, read at creation), else the form the
+ *     measured A/B prefers (the SVD section).
+ * Memory: B and B' both stay resident (the caller's A is one of them, the
+ * object owns the other: 12 B an entry), plus, where the fused form is
+ * planned, its layout (10 B a stored entry) and the partials (workgroups x k
+ * doubles), plus one vector of max(m, n) doubles.  The scratch belongs to the
+ * object: one stream per object at a time.  A must outlive S.
+ * 0; -1 bad argument (form 2 with k > fused_kmax, a column index outside the
+ * shape); -2 a HIP call or plan failed (nothing is kept). */
+typedef struct arpack_hip_dsvd arpack_hip_dsvd;
+int arpack_hip_dsvd_create(arpack_hip_dsvd** S, const arpack_hip_csr* A, int form);
+void arpack_hip_dsvd_destroy(arpack_hip_dsvd* S);
+/* y = B'(B x): x, y distinct device vectors of k doubles; complete on return.
+ * Every entry of y is written (a column no row touches gives 0). */
+int arpack_hip_dsvd_apply(arpack_hip_dsvd* S, const double* x, double* y);
+/* Shape, the form apply runs (1 or 2) and the fused form's largest k. */
+int arpack_hip_dsvd_info(const arpack_hip_dsvd* S, int64_t* m, int64_t* n, int64_t* k, int* form,
+                         int64_t* fused_kmax);
+/* Average device time (ms, hipEvents) of `reps` back-to-back applies. */
+double arpack_hip_dsvd_time(arpack_hip_dsvd* S, const double* x, double* y, int reps);
+/* dsaupd_c with OP = B'B served on the GPU, a free run like
+ * arpack_hip_dsaupd_csr: n = k, mode 1 and bmat 'I' only (else info = -11),
+ * dseupd_c afterwards returns lambda = sigma^2 and the vectors on the short
+ * side.  A HIP error ends it with info = -9999. */
+void arpack_hip_dsaupd_svd(arpack_hip_dsvd* S, int* ido, char const* bmat, int n, char const* which,
+                           int nev, double tol, double* resid, int ncv, double* v, int ldv,
+                           int* iparam, int* ipntr, double* workd, double* workl, int lworkl,
+                           int* info);
+/* Post-processing (dsvd.f:416-450) for the nconv Ritz pairs (d host, Z device
+ * k x nconv, ldz): sigma_out[j] = sqrt(max(d[j], 0)) (host), Uother(:, j) =
+ * B z_j / ||B z_j|| (device, max(m, n) x nconv, ldu) and resid_out[j] =
+ * ||B z_j - sigma_j u_j|| (host).  For m >= n Z holds the right and Uother the
+ * left singular vectors; for m < n the other way round.  0; -1; -2 HIP error. */
+int arpack_hip_dsvd_vectors(arpack_hip_dsvd* S, int nconv, const double* d, const double* Z,
+                            int64_t ldz, double* sigma_out, double* Uother, int64_t ldu,
+                            double* resid_out);
+/* The engine's dsaupd argument checks alone (SRC/dsaupd.f:501-543; host only):
+ * the info code dsaupd_c would return at ido = 0, 0 when the arguments pass. */
+int arpack_hip_dsaupd_check(char const* bmat, int n, char const* which, int nev, int ncv,
+                            int lworkl, int mode, int ishift, int mxiter);
+
 /* Complex CSR operator (rowptr int64[n+1], col int32[nnz], val complex128[nnz]
  * interleaved) and the complex random operator of BASELINE config 5 (SURVEY.md
  * §8d S5: per_row hashed columns, U(-1,1)+iU(-1,1) on a 2^-10 grid, duplicate
