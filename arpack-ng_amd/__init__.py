@@ -179,6 +179,17 @@ def _declare(L):
     L.ssaupd_.argtypes = _f32(L.dsaupd_.argtypes, [5])
     L.snaupd_.argtypes = _f32(L.dnaupd_.argtypes, [5])
     L.sseupd_c.argtypes = _f32(L.dseupd_c.argtypes, [6, 11])
+    # fp32 device operator and the s family's free run on it
+    L.arpack_hip_csr_create_f32.argtypes = L.arpack_hip_csr_create.argtypes
+    L.arpack_hip_csr_precision.argtypes = [C.c_void_p]
+    L.arpack_hip_csr_spmv_f32.argtypes = L.arpack_hip_csr_spmv.argtypes
+    L.arpack_hip_csr_time_f32.argtypes = L.arpack_hip_csr_time.argtypes
+    L.arpack_hip_csr_time_f32.restype = C.c_double
+    L.arpack_hip_csr_download_f32.argtypes = L.arpack_hip_csr_download.argtypes
+    L.arpack_hip_csr_set_sym_accumulator.argtypes = [C.c_void_p, C.c_int]
+    L.arpack_hip_ssaupd_csr.argtypes = _f32(L.arpack_hip_dsaupd_csr.argtypes, [6])
+    L.arpack_hip_ssaupd_csr_cycles.argtypes = _f32(L.arpack_hip_dsaupd_csr_cycles.argtypes, [7])
+    L.arpack_hip_snaupd_csr_cycles.argtypes = L.arpack_hip_ssaupd_csr_cycles.argtypes
     L.sneupd_c.argtypes = _f32(L.dneupd_c.argtypes, [7, 8, 14])
 
 
@@ -328,6 +339,10 @@ class CSR:
         # (nrows, x length): a row block of a distributed operator reads an
         # x longer than its rows too; only from_arrays(shape=) makes `rect`
         self.shape = (n.value, nc.value)
+        # float32: an fp32 operator (from_arrays(dtype=np.float32)), the OP of
+        # the s family's free run; float64: everything else
+        self.dtype = np.dtype(np.float32 if lib().arpack_hip_csr_precision(self.h) == ord("s")
+                              else np.float64)
         self._owner = owner
 
     def __del__(self):
@@ -339,14 +354,29 @@ class CSR:
             pass
 
     @classmethod
-    def from_arrays(cls, rowptr, col, val, shape=None):
+    def from_arrays(cls, rowptr, col, val, shape=None, dtype=None):
         """shape=(nrows, ncols): a rectangular operator
         (arpack_hip_csr_create_rect; column indices checked against ncols) for
-        the product and svds; None: the square operator of the solvers."""
+        the product and svds; None: the square operator of the solvers.
+        dtype=np.float32: the values are stored as float32
+        (arpack_hip_csr_create_f32, square only) -- the operator of
+        SymRci / NsRci(prec="s") free runs and of eigsh / eigs in single
+        precision; None (or float64) stores float64 whatever val's dtype."""
         rowptr = np.ascontiguousarray(rowptr, np.int64)
         col = np.ascontiguousarray(col, np.int32)
-        val = np.ascontiguousarray(val, np.float64)
         h = C.c_void_p()
+        if dtype is not None and np.dtype(dtype) == np.float32:
+            if shape is not None:
+                raise ValueError("a float32 operator is square: dtype=np.float32 takes no shape=")
+            val = np.ascontiguousarray(val, np.float32)
+            rc = lib().arpack_hip_csr_create_f32(C.byref(h), len(rowptr) - 1, len(col),
+                                                 rowptr.ctypes.data, col.ctypes.data, val.ctypes.data)
+            if rc != 0:
+                raise RuntimeError("arpack_hip_csr_create_f32 failed (rc=%d)" % rc)
+            return cls(h.value)
+        if dtype is not None and np.dtype(dtype) != np.float64:
+            raise ValueError("dtype must be float32 or float64")
+        val = np.ascontiguousarray(val, np.float64)
         if shape is not None:
             nr, nc = int(shape[0]), int(shape[1])
             if nr != len(rowptr) - 1:
@@ -417,8 +447,11 @@ class CSR:
     def download(self):
         rowptr = np.empty(self.n + 1, np.int64)
         col = np.empty(self.nnz, np.int32)
-        val = np.empty(self.nnz, np.float64)
-        lib().arpack_hip_csr_download(self.h, rowptr.ctypes.data, col.ctypes.data, val.ctypes.data)
+        val = np.empty(self.nnz, self.dtype)
+        f = (lib().arpack_hip_csr_download_f32 if self.dtype == np.float32
+             else lib().arpack_hip_csr_download)
+        if f(self.h, rowptr.ctypes.data, col.ctypes.data, val.ctypes.data) != 0:
+            raise RuntimeError("csr download failed")
         return rowptr, col, val
 
     def set_kernel(self, kernel: int, tile: int = 4096):
@@ -446,7 +479,6 @@ class CSR:
         """The symmetric kernel's transposed-term accumulator: "fixed" (the
         fixed-point form, bitwise reproducible; default) or "fp64" (LDS fp64
         atomics in schedule order) -- arpack_hip_csr_set_sym_accumulator."""
-        lib().arpack_hip_csr_set_sym_accumulator.argtypes = [C.c_void_p, C.c_int]
         if lib().arpack_hip_csr_set_sym_accumulator(self.h, {"fixed": 0, "fp64": 1}[acc]) != 0:
             raise RuntimeError("set_sym_accumulator failed")
 
@@ -458,16 +490,22 @@ class CSR:
         return ("full", "sym_fp64", "sym_fixed")[lib().arpack_hip_csr_sym_form(self.h)]
 
     def time_spmv(self, reps=20):
-        x = DeviceBuffer(self.shape[1])
+        x = DeviceBuffer(self.shape[1], self.dtype)
         x.write(np.linspace(-1, 1, self.shape[1]))
-        y = DeviceBuffer(self.n)
-        return lib().arpack_hip_csr_time(self.h, x.ptr, y.ptr, reps)
+        y = DeviceBuffer(self.n, self.dtype)
+        f = lib().arpack_hip_csr_time_f32 if self.dtype == np.float32 else lib().arpack_hip_csr_time
+        return f(self.h, x.ptr, y.ptr, reps)
 
     def matvec_device(self, x, y):
-        """y = A x for device addresses (ints) or DeviceBuffers."""
+        """y = A x for device addresses (ints) or DeviceBuffers of the
+        operator's dtype (a DeviceBuffer of another dtype raises ValueError)."""
+        for b in (x, y):
+            if isinstance(b, DeviceBuffer) and b.dtype != self.dtype:
+                raise ValueError("a %s operator takes %s vectors" % (self.dtype, self.dtype))
         xp = x if isinstance(x, int) else _ptr(x)
         yp = y if isinstance(y, int) else _ptr(y)
-        if lib().arpack_hip_csr_spmv(self.h, xp, yp) != 0:
+        f = lib().arpack_hip_csr_spmv_f32 if self.dtype == np.float32 else lib().arpack_hip_csr_spmv
+        if f(self.h, xp, yp) != 0:
             raise RuntimeError("spmv failed")
 
 
@@ -540,26 +578,38 @@ class SymRci:
             self.tol = tol.value
         return int(self.ido[0])
 
+    def _check_prec(self, A: CSR):
+        """The operator's values are the family's precision (before the call)."""
+        if A.dtype != np.dtype(self.dt):
+            raise ValueError("prec=%r needs a %s operator, got %s (CSR.from_arrays(dtype=))"
+                             % (self.prec, np.dtype(self.dt), A.dtype))
+
     def aupd_csr(self, A: CSR):
-        """Run to completion with OP = A on the GPU (arpack_hip_dsaupd_csr)."""
-        lib().arpack_hip_dsaupd_csr(A.h, _ip(self.ido), self.bmat.encode(), self.n,
-                                    self.which.encode(), self.nev, self.tol, _ptr(self.resid),
-                                    self.ncv, _ptr(self.v), self.ldv, _ip(self.iparam),
-                                    _ip(self.ipntr), _ptr(self.workd), self.workl.ctypes.data,
-                                    self.lworkl, _ip(self.info))
+        """Run to completion with OP = A on the GPU (arpack_hip_dsaupd_csr;
+        prec="s" on a float32 operator: arpack_hip_ssaupd_csr)."""
+        self._check_prec(A)
+        f = getattr(lib(), "arpack_hip_%ssaupd_csr" % self.prec)
+        f(A.h, _ip(self.ido), self.bmat.encode(), self.n,
+          self.which.encode(), self.nev, self.tol, _ptr(self.resid),
+          self.ncv, _ptr(self.v), self.ldv, _ip(self.iparam),
+          _ip(self.ipntr), _ptr(self.workd), self.workl.ctypes.data,
+          self.lworkl, _ip(self.info))
         if self.tol <= 0.0:  # the solve used eps (SRC/dsaupd.f:550); keep it for dseupd
-            self.tol = float(np.finfo(np.float64).eps / 2)
+            self.tol = float(np.finfo(self.dt).eps / 2)
         return int(self.ido[0])
 
     def aupd_cycles(self, A: CSR, max_cycles: int):
         """Free-running solve that parks (ido=98) after `max_cycles` more restart
-        cycles (arpack_hip_dsaupd_csr_cycles); returns ido (98 parked, 99 done)."""
-        tol = C.c_double(self.tol)
-        lib().arpack_hip_dsaupd_csr_cycles(A.h, int(max_cycles), _ip(self.ido), self.bmat.encode(),
-                                           self.n, self.which.encode(), self.nev, C.byref(tol),
-                                           _ptr(self.resid), self.ncv, _ptr(self.v), self.ldv,
-                                           _ip(self.iparam), _ip(self.ipntr), _ptr(self.workd),
-                                           self.workl.ctypes.data, self.lworkl, _ip(self.info))
+        cycles (arpack_hip_dsaupd_csr_cycles / _ssaupd_csr_cycles); returns ido
+        (98 parked, 99 done)."""
+        self._check_prec(A)
+        tol = (C.c_float if self.prec == "s" else C.c_double)(self.tol)
+        f = getattr(lib(), "arpack_hip_%s%saupd_csr_cycles" % (self.prec, self._fam))
+        f(A.h, int(max_cycles), _ip(self.ido), self.bmat.encode(),
+          self.n, self.which.encode(), self.nev, C.byref(tol),
+          _ptr(self.resid), self.ncv, _ptr(self.v), self.ldv,
+          _ip(self.iparam), _ip(self.ipntr), _ptr(self.workd),
+          self.workl.ctypes.data, self.lworkl, _ip(self.info))
         self.tol = tol.value
         return int(self.ido[0])
 
@@ -651,16 +701,6 @@ class NsRci(SymRci):
         self.lworkl = 3 * ncv * ncv + 6 * ncv
         self.workl = np.zeros(self.lworkl, self.dt)
 
-    def aupd_cycles(self, A: CSR, max_cycles: int):
-        tol = C.c_double(self.tol)
-        lib().arpack_hip_dnaupd_csr_cycles(A.h, int(max_cycles), _ip(self.ido), self.bmat.encode(),
-                                           self.n, self.which.encode(), self.nev, C.byref(tol),
-                                           _ptr(self.resid), self.ncv, _ptr(self.v), self.ldv,
-                                           _ip(self.iparam), _ip(self.ipntr), _ptr(self.workd),
-                                           self.workl.ctypes.data, self.lworkl, _ip(self.info))
-        self.tol = tol.value
-        return int(self.ido[0])
-
     def aupd_gen(self, G: "DGen"):
         """Whole loop on the GPU in dnaupd's generalized modes (bmat="G", mode
         2, or 3 with G's real sigma): OP*x and B*x by the device operator pair
@@ -691,7 +731,7 @@ class NsRci(SymRci):
     def aupd_csr(self, A: CSR):
         r = self.aupd_cycles(A, -1)
         if self.tol <= 0.0:
-            self.tol = float(np.finfo(np.float64).eps / 2)
+            self.tol = float(np.finfo(self.dt).eps / 2)
         return r
 
     def eupd(self, rvec=True, howmny="A", sigmar=0.0, sigmai=0.0, z=None, dist=None):
@@ -1114,8 +1154,12 @@ def eigsh(op, n, nev=6, ncv=None, which="LM", tol=0.0, v0=None, mxiter=300, rvec
         raise ValueError("sigma needs a CSR operator (the device solve); with a callable, "
                          "drive SymRci(mode=3) and apply (A - sigma I)^{-1} yourself")
     shift = sigma is not None
+    f32 = isinstance(op, CSR) and op.dtype == np.float32
+    if f32 and shift:
+        raise ValueError("sigma needs a float64 operator: the device solves are fp64")
+    # a float32 CSR: the s family's free run (float32 d / Z, tol <= 0 -> eps_f)
     s = SymRci(n, nev, ncv, which, tol, mode=3 if shift else 1, mxiter=mxiter, v0=v0,
-               device=device)
+               device=device, prec="s" if f32 else "d")
     if shift:
         S = DShift(op, sigma, rtol=rtol, maxit=maxit, method=solver)
         s.aupd_shift(S)
@@ -1202,7 +1246,12 @@ def eigs(op, n, nev=6, ncv=None, which="LM", tol=0.0, v0=None, mxiter=300, rvec=
         raise ValueError("sigma needs a CSR or ZCSR operator (the device solve); with a "
                          "callable, drive NsRci(mode=3) and apply (A - sigma I)^{-1} yourself")
     shift = sigma is not None
-    s = NsRci(n, nev, ncv, which, tol, mode=3 if shift else 1, mxiter=mxiter, v0=v0)
+    f32 = isinstance(op, CSR) and op.dtype == np.float32
+    if f32 and shift:
+        raise ValueError("sigma needs a float64 operator: the device solves are fp64")
+    # a float32 CSR: the s family's free run (complex64 d, tol <= 0 -> eps_f)
+    s = NsRci(n, nev, ncv, which, tol, mode=3 if shift else 1, mxiter=mxiter, v0=v0,
+              prec="s" if f32 else "d")
     if shift:  # real shift-invert: OP = (A - sigma I)^{-1} by the device BiCGStab
         S = DShift(op, float(sigma), rtol=rtol, maxit=maxit, method="bicgstab")
         s.aupd_shift(S)
@@ -1225,7 +1274,11 @@ def eigs(op, n, nev=6, ncv=None, which="LM", tol=0.0, v0=None, mxiter=300, rvec=
                nopx=int(s.iparam[8]))
     dr, di, z, nconv = s.eupd(rvec=rvec, sigmar=float(sigma) if shift else 0.0)
     d = dr + 1j * di
-    return d, (_ns_vectors(dr, di, z, n, nconv) if rvec else None), res
+    Z = _ns_vectors(dr, di, z, n, nconv) if rvec else None
+    if f32:  # single precision in, single precision out
+        d = d.astype(np.complex64)
+        Z = Z.astype(np.complex64) if rvec else None
+    return d, Z, res
 
 
 # ------------------------------------------------------------- truncated SVD

@@ -19,6 +19,7 @@
 const ahip::dev::Csr* ahip_csr_view(const arpack_hip_csr* A);
 const ahip::DistOp* ahip_dist_view(const arpack_hip_dist* D);
 bool ahip_csr_is_rect(const arpack_hip_csr* A);
+bool ahip_csr_is_f32(const arpack_hip_csr* A);
 
 namespace ahip {
 
@@ -144,8 +145,11 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
     if (dist) csr = dist->A;
     if (shift) csr = shift->A;  // mode 3 free run: OP = (A - sigma I)^{-1} on the device
     if (gen) csr = gen->A;      // modes 2-5, bmat = 'G': OP and B on the device
-    if (kShadow && csr) {  // the float family: reverse communication (no device-CSR OP)
-        *info = -9999;
+    // the operator's precision is the family's: d* / p* entries serve an fp64
+    // operator, the s* entries an fp32 one (arpack_hip_csr_create_f32: mode 1,
+    // bmat = 'I', one GPU) -- the bad-argument return, before anything runs
+    if (csr && (kShadow != (csr->prec == 's') || (kShadow && (dist || shift || gen || svd)))) {
+        *info = -11;
         *ido = 99;
         return;
     }
@@ -398,9 +402,14 @@ static void sym_aupd(int* ido, const char* bmat, int n, const char* which, int n
                     continue;
                 }
             }
+            // the float family's product carries no finalize (its steps are the
+            // plain ones): a deferred one is launched first
+            if constexpr (kShadow) dev::flush_deferred_finalize(S->ws.defq, S->a.stream);
             if (S->dist) dev::prof_begin(dev::kProfSpmv, S->a.stream);
             else dev::prof_arm(dev::kProfSpmv, S->a.stream);
-            if constexpr (!kShadow) {
+            if constexpr (kShadow) {
+                dev::csr_spmv_f32(S->a.stream, *S->csr, S->op_x, S->op_y);
+            } else {
                 if (S->dist) dist_spmv(*S->dist, S->a.stream, S->op_x, S->op_y, false, S->ws.defq);
                 else dev::csr_spmv(S->a.stream, *S->csr, S->op_x, S->op_y, S->ws.defq);
             }
@@ -556,6 +565,37 @@ void arpack_hip_dsaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* 
              info, ahip_csr_view(A), max_cycles);
 }
 
+// ---- the single-precision family's free run on an fp32 device operator ------
+// (arpack_hip_csr_create_f32; an fp64 operator ends with info = -11)
+void arpack_hip_ssaupd_csr(const arpack_hip_csr* A, int* ido, char const* bmat, int n,
+                           char const* which, int nev, float tol, float* resid, int ncv, float* v,
+                           int ldv, int* iparam, int* ipntr, float* workd, float* workl, int lworkl,
+                           int* info) {
+    double t = tol;
+    sym_aupd(ido, bmat, n, which, nev, &t, resid, ncv, v, ldv, iparam, ipntr, workd, workl, lworkl,
+             info, ahip_csr_view(A));
+}
+
+void arpack_hip_ssaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* ido,
+                                  char const* bmat, int n, char const* which, int nev, float* tol,
+                                  float* resid, int ncv, float* v, int ldv, int* iparam, int* ipntr,
+                                  float* workd, float* workl, int lworkl, int* info) {
+    double t = *tol;
+    sym_aupd(ido, bmat, n, which, nev, &t, resid, ncv, v, ldv, iparam, ipntr, workd, workl, lworkl,
+             info, ahip_csr_view(A), max_cycles);
+    *tol = (float)t;
+}
+
+void arpack_hip_snaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* ido,
+                                  char const* bmat, int n, char const* which, int nev, float* tol,
+                                  float* resid, int ncv, float* v, int ldv, int* iparam, int* ipntr,
+                                  float* workd, float* workl, int lworkl, int* info) {
+    double t = *tol;
+    sym_aupd(ido, bmat, n, which, nev, &t, resid, ncv, v, ldv, iparam, ipntr, workd, workl, lworkl,
+             info, ahip_csr_view(A), max_cycles, nullptr, true);
+    *tol = (float)t;
+}
+
 // ---- shift-invert on the device (dsaupd mode 3, dshift.hip) ----------------
 struct arpack_hip_dshift {
     ahip::dev::DShift S;
@@ -653,7 +693,7 @@ void arpack_hip_dnaupd_gen(arpack_hip_dgen* D, int* ido, char const* bmat, int n
 
 int arpack_hip_dshift_create(arpack_hip_dshift** out, const arpack_hip_csr* A, double sigma,
                              double rtol, int maxit) {
-    if (!out || !A || ahip_csr_is_rect(A) || !(rtol > 0.0) || maxit < 1) return -1;
+    if (!out || !A || ahip_csr_is_rect(A) || ahip_csr_is_f32(A) || !(rtol > 0.0) || maxit < 1) return -1;
     auto* D = new arpack_hip_dshift;
     if (ahip::dev::dshift_create(D->S, ahip_csr_view(A), sigma, rtol, maxit) != 0) {
         delete D;

@@ -357,6 +357,73 @@ int arpack_hip_csr_create_rect(arpack_hip_csr** out, int64_t nrows, int64_t ncol
     return rc;
 }
 
+int arpack_hip_csr_create_f32(arpack_hip_csr** out, int64_t n, int64_t nnz, const int64_t* rowptr,
+                              const int32_t* col, const float* val) {
+    if (!out || n < 1 || n > (int64_t)INT32_MAX || nnz < 0 || !rowptr || (nnz > 0 && (!col || !val)))
+        return -1;
+    // every index is checked before a kernel gathers x with it (host copies;
+    // the pointers may be device ones)
+    std::vector<int64_t> hrp((size_t)n + 1);
+    std::vector<int32_t> hc((size_t)nnz);
+    if (hipMemcpy(hrp.data(), rowptr, sizeof(int64_t) * (n + 1), hipMemcpyDefault) != hipSuccess ||
+        (nnz > 0 && hipMemcpy(hc.data(), col, sizeof(int32_t) * nnz, hipMemcpyDefault) != hipSuccess))
+        return -1;
+    if (hrp[0] != 0 || hrp[n] != nnz) return -1;
+    for (int64_t i = 0; i < n; ++i)
+        if (hrp[i + 1] < hrp[i]) return -1;
+    for (int64_t k = 0; k < nnz; ++k)
+        if (hc[k] < 0 || hc[k] >= n) return -1;
+    auto* A = new arpack_hip_csr;
+    const bool ok =
+        hipMalloc(&A->rowptr, sizeof(int64_t) * (n + 1)) == hipSuccess &&
+        hipMalloc(&A->col, sizeof(int32_t) * (nnz > 0 ? nnz : 1)) == hipSuccess &&
+        hipMalloc(&A->valf, sizeof(float) * (nnz > 0 ? nnz : 1)) == hipSuccess &&
+        hipMemcpy(A->rowptr, hrp.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess &&
+        (nnz == 0 ||
+         (hipMemcpy(A->col, hc.data(), sizeof(int32_t) * nnz, hipMemcpyHostToDevice) == hipSuccess &&
+          hipMemcpy(A->valf, val, sizeof(float) * nnz, hipMemcpyDefault) == hipSuccess));
+    if (!ok) {
+        arpack_hip_csr_destroy(A);
+        return -1;
+    }
+    A->ncols = n;
+    A->A.n = n;
+    A->A.nnz = nnz;
+    A->A.rowptr = A->rowptr;
+    A->A.col = A->col;
+    A->A.prec = 's';
+    A->A.valf = A->valf;
+    A->A.group = pick_group(n, nnz);
+    A->A.kernel = ahip::dev::kCsrVector;
+    // the fp64 operator's planners (index-only): LDS x windows, single- or
+    // multi-range, then the SELL-64 layout over them with float values.  No
+    // CSR-stream row blocks: the fp32 forms are SELL and the vector fallback.
+    if (analyse_window_sell(A, n) == -2) {
+        arpack_hip_csr_destroy(A);
+        return -2;
+    }
+    // the 16-bit columns in CSR order served the SELL build only (no fp32
+    // kernel reads them), and without a SELL layout the window tables serve
+    // nothing: neither stays resident
+    if (A->A.w_colw) (void)hipFree((void*)A->A.w_colw);
+    A->A.w_colw = nullptr;
+    if (A->A.kernel == ahip::dev::kCsrSell) {
+        A->A.s_unroll = 6;  // column steps a chunk
+    } else {
+        if (A->win) (void)hipFree(A->win);
+        A->win = nullptr;
+        A->A.w_tiles = A->A.w_sb_tile0 = A->A.w_sb_c0 = nullptr;
+        A->A.w_sb_span = nullptr;
+        A->A.w_rng = nullptr;
+        A->A.w_nsb = 0;
+        A->A.kernel = ahip::dev::kCsrVector;
+    }
+    *out = A;
+    return 0;
+}
+
+int arpack_hip_csr_precision(const arpack_hip_csr* A) { return A ? (int)A->A.prec : -1; }
+
 int arpack_hip_csr_shape(const arpack_hip_csr* A, int64_t* nrows, int64_t* ncols) {
     if (!A) return -1;
     if (nrows) *nrows = A->A.n;
@@ -378,6 +445,7 @@ void arpack_hip_csr_destroy(arpack_hip_csr* A) {
     (void)hipFree(A->rowptr);
     (void)hipFree(A->col);
     (void)hipFree(A->val);
+    (void)hipFree(A->valf);
     if (A->rblk) (void)hipFree(A->rblk);
     if (A->win) (void)hipFree(A->win);
     if (A->sell) (void)hipFree(A->sell);
@@ -401,6 +469,7 @@ int arpack_hip_csr_info(const arpack_hip_csr* A, int64_t* n, int64_t* nnz) {
 }
 
 int arpack_hip_csr_download(const arpack_hip_csr* A, int64_t* rowptr, int32_t* col, double* val) {
+    if (!A || A->A.prec == 's') return -1;  // float values: arpack_hip_csr_download_f32
     const bool ok =
         hipMemcpy(rowptr, A->rowptr, sizeof(int64_t) * (A->A.n + 1), hipMemcpyDeviceToHost) == hipSuccess &&
         (A->A.nnz == 0 ||
@@ -409,7 +478,46 @@ int arpack_hip_csr_download(const arpack_hip_csr* A, int64_t* rowptr, int32_t* c
     return ok ? 0 : -1;
 }
 
+int arpack_hip_csr_download_f32(const arpack_hip_csr* A, int64_t* rowptr, int32_t* col, float* val) {
+    if (!A || A->A.prec != 's') return -1;
+    const bool ok =
+        hipMemcpy(rowptr, A->rowptr, sizeof(int64_t) * (A->A.n + 1), hipMemcpyDeviceToHost) == hipSuccess &&
+        (A->A.nnz == 0 ||
+         (hipMemcpy(col, A->col, sizeof(int32_t) * A->A.nnz, hipMemcpyDeviceToHost) == hipSuccess &&
+          hipMemcpy(val, A->valf, sizeof(float) * A->A.nnz, hipMemcpyDeviceToHost) == hipSuccess));
+    return ok ? 0 : -1;
+}
+
+int arpack_hip_csr_spmv_f32(const arpack_hip_csr* A, const float* x, float* y) {
+    if (!A || A->A.prec != 's' || !x || !y) return -1;  // (an fp64 operator: arpack_hip_csr_spmv)
+    // as arpack_hip_csr_spmv: the caller's own stream first, y complete on return
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    ahip::dev::csr_spmv_f32(nullptr, A->A, x, y);
+    return hipStreamSynchronize(nullptr) == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+double arpack_hip_csr_time_f32(const arpack_hip_csr* A, const float* x, float* y, int reps) {
+    if (!A || A->A.prec != 's' || !x || !y || reps < 1) return -1.0;
+    hipEvent_t a, b;
+    if (hipEventCreate(&a) != hipSuccess) return -1.0;
+    if (hipEventCreate(&b) != hipSuccess) {
+        (void)hipEventDestroy(a);
+        return -1.0;
+    }
+    ahip::dev::csr_spmv_f32(nullptr, A->A, x, y);  // warm
+    (void)hipEventRecord(a, nullptr);
+    for (int r = 0; r < reps; ++r) ahip::dev::csr_spmv_f32(nullptr, A->A, x, y);
+    (void)hipEventRecord(b, nullptr);
+    (void)hipEventSynchronize(b);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, a, b);
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return (double)ms / reps;
+}
+
 int arpack_hip_csr_spmv(const arpack_hip_csr* A, const double* x, double* y) {
+    if (A->A.prec == 's') return -1;  // fp64 vectors: an fp32 operator has arpack_hip_csr_spmv_f32
     // x may come from the caller's own GPU work on a non-blocking stream, which
     // the null stream does not order against: complete it first
     if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -426,6 +534,7 @@ static void csr_full_storage(arpack_hip_csr* A) {
 
 int arpack_hip_csr_set_symmetric(arpack_hip_csr* A, int on) {
     if (A->rect) return -1;  // symmetric storage is a square operator's
+    if (A->A.prec == 's') return -1;  // ... and an fp64 one's
     // one rank's block of a distributed operator: the symmetric SpMV changes the
     // exchange pattern (hi-only halo + forward spill), so the switch -- either
     // way -- is collective, and every rank falls back to full storage if any
@@ -481,7 +590,7 @@ int arpack_hip_csr_set_symmetric(arpack_hip_csr* A, int on) {
 }
 
 int arpack_hip_csr_set_sym_accumulator(arpack_hip_csr* A, int acc) {
-    if (!A || (acc != 0 && acc != 1)) return -1;
+    if (!A || (acc != 0 && acc != 1) || A->A.prec == 's') return -1;
     A->A.ss_acc = acc;
     return 0;
 }
@@ -493,6 +602,18 @@ int arpack_hip_csr_sym_form(const arpack_hip_csr* A) {
 }
 
 int arpack_hip_csr_set_kernel(arpack_hip_csr* A, int kernel, int tile) {
+    if (A->A.prec == 's') {  // an fp32 operator: the forms with an fp32 kernel only
+        if (kernel == ahip::dev::kCsrVector) {
+            A->A.kernel = kernel;
+            return 0;
+        }
+        if (kernel == ahip::dev::kCsrSell && A->sell) {  // tile selects the unroll (4 or 6)
+            A->A.kernel = kernel;
+            A->A.s_unroll = tile == 4 ? 4 : 6;
+            return 0;
+        }
+        return -1;
+    }
     if (kernel == ahip::dev::kCsrSymSell) {  // tile selects the variant
         const int rc = arpack_hip_csr_set_symmetric(A, 1);
         if (rc == 0) A->A.ss_variant = tile >= 0 && tile <= 16 ? tile : 0;
@@ -525,6 +646,7 @@ int arpack_hip_csr_set_kernel(arpack_hip_csr* A, int kernel, int tile) {
 }
 
 double arpack_hip_csr_time(const arpack_hip_csr* A, const double* x, double* y, int reps) {
+    if (A->A.prec == 's') return -1.0;  // arpack_hip_csr_time_f32
     hipEvent_t a, b;
     (void)hipEventCreate(&a);
     (void)hipEventCreate(&b);
@@ -627,6 +749,7 @@ int arpack_hip_gen_banded_sym(arpack_hip_csr** out, int64_t n, int64_t r0, int64
 
 const ahip::dev::Csr* ahip_csr_view(const arpack_hip_csr* A) { return &A->A; }
 bool ahip_csr_is_rect(const arpack_hip_csr* A) { return A && A->rect; }
+bool ahip_csr_is_f32(const arpack_hip_csr* A) { return A && A->A.prec == 's'; }
 int64_t ahip_csr_ncols(const arpack_hip_csr* A) { return A->ncols; }
 
 // ------------------------------------------------------------ remap helpers --

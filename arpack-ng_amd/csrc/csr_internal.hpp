@@ -14,6 +14,10 @@ struct arpack_hip_csr {
     int64_t* rowptr = nullptr;
     int32_t* col = nullptr;
     double* val = nullptr;
+    // an fp32 operator's values (arpack_hip_csr_create_f32; val is then null and
+    // A.prec == 's'): it serves arpack_hip_csr_spmv_f32 and the s* free runs,
+    // and every fp64 entry refuses it
+    float* valf = nullptr;
     int64_t row_begin = 0;  // global index of local row 0 (sharded generators)
     int64_t ncols = 0;
     int64_t* rblk = nullptr;  // CSR-stream row blocks (owned)
@@ -37,6 +41,8 @@ struct arpack_hip_csr {
 
 // a rectangular operator (arpack_hip_csr_create_rect, nrows != ncols)
 bool ahip_csr_is_rect(const arpack_hip_csr* A);
+// an fp32 operator (arpack_hip_csr_create_f32)
+bool ahip_csr_is_f32(const arpack_hip_csr* A);
 // length of the x vector A's product reads
 int64_t ahip_csr_ncols(const arpack_hip_csr* A);
 

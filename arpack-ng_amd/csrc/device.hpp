@@ -270,6 +270,12 @@ struct Csr {
     const int64_t* rowptr = nullptr;  // n+1
     const int32_t* col = nullptr;     // nnz
     const double* val = nullptr;      // nnz
+    // 's': an fp32 operator (arpack_hip_csr_create_f32) -- the values live in
+    // valf / s_valf only (val, s_val stay null: no fp64 copy is resident) and
+    // csr_spmv_f32 is its product; 'd': everything else
+    char prec = 'd';
+    const float* valf = nullptr;      // nnz
+    const float* s_valf = nullptr;    // SELL-64 values (the layout of s_val)
     int group = 16;                   // lanes per row for the vector kernel
     // CSR-stream row blocks: block b owns rows [rblk[b], rblk[b+1]) whose
     // nonzeros (<= tile) are streamed by one workgroup
@@ -407,12 +413,18 @@ int csr_analyse_ranges(Csr& A, int64_t ncols, void** owned);
 // is longer than the tile (the matrix then keeps the vector kernel).
 int csr_analyse(Csr& A, int tile, int64_t** rblk_dev);
 void csr_spmv(hipStream_t s, const Csr& A, const double* x, double* y, FinQueue* q = nullptr);
+// y = A x of an fp32 operator (A.prec == 's') on fp32 vectors: every row summed
+// in fp64 and rounded once on the store.  kCsrSell (k_csr_sell_f32: in column
+// order, bitwise (A32 in fp64) @ (x in fp64) rounded to fp32) or kCsrVector
+// (fixed lane-tree order).  Carries no deferred finalize: flush it first.
+void csr_spmv_f32(hipStream_t s, const Csr& A, const float* x, float* y);
 // the first superblock / chain lighter (its workgroup carries the deferred
 // finalize); false under AHIP_LIGHT_SB=0
 bool light_first_sb();
 // AHIP_LIGHT_SB=2: the light superblock 0 shortened by 8% of a chain (A/B)
 bool light_sb_chain();
 // algorithmic HBM bytes of one SpMV: 12*nnz + 8*(n+1) (int64 rowptr) + 8n (x) + 8n (y)
+// (an fp32 operator's SELL form: 6*nnz + 4n row map + 4n x windows + 4n y)
 double csr_bytes(const Csr& A);
 // deterministic mode on a symmetric-storage operator whose fixed-point form is
 // not available (on some rank): the SpMV runs the full-storage kernel instead

@@ -30,6 +30,7 @@
 
 const ahip::dev::Csr* ahip_csr_view(const arpack_hip_csr* A);  // csr.hip
 bool ahip_csr_is_rect(const arpack_hip_csr* A);
+bool ahip_csr_is_f32(const arpack_hip_csr* A);  // (the device solves are fp64)
 const ahip::zdev::ZCsr* ahip_zcsr_view(const arpack_hip_zcsr* A);  // zsolver.cpp
 
 namespace ahip::dev {
@@ -91,7 +92,7 @@ int dgen_create(DGen& G, const arpack_hip_csr* A, const arpack_hip_csr* B, int m
     int64_t na = 0, nb = 0, nz = 0;
     if (!A || !B || mode < 2 || mode > 5 || arpack_hip_csr_info(A, &na, &nz) != 0 ||
         arpack_hip_csr_info(B, &nb, &nz) != 0 || na != nb || na <= 0 || ahip_csr_is_rect(A) ||
-        ahip_csr_is_rect(B))
+        ahip_csr_is_rect(B) || ahip_csr_is_f32(A) || ahip_csr_is_f32(B))
         return -1;
     G.A = ahip_csr_view(A);
     G.B = ahip_csr_view(B);
@@ -134,7 +135,7 @@ int dgen_create_cshift(DGen& G, const arpack_hip_csr* A, const arpack_hip_csr* B
     int64_t na = 0, nb = 0, nz = 0;
     if (!A || !B || (mode != 3 && mode != 4) || sigmai == 0.0 || method < 0 || method > 1 ||
         arpack_hip_csr_info(A, &na, &nz) != 0 || arpack_hip_csr_info(B, &nb, &nz) != 0 || na != nb ||
-        na <= 0 || ahip_csr_is_rect(A) || ahip_csr_is_rect(B))
+        na <= 0 || ahip_csr_is_rect(A) || ahip_csr_is_rect(B) || ahip_csr_is_f32(A) || ahip_csr_is_f32(B))
         return -1;
     G.A = ahip_csr_view(A);
     G.B = ahip_csr_view(B);

@@ -267,9 +267,11 @@ int arpack_hip_dist_create(arpack_hip_dist** out, arpack_hip_csr* A, int64_t n_g
     const int P = comm_size(c), r = comm_rank(c);
     const int64_t nloc = A->A.n;
     int64_t cmin = 0, cmax = -1;
-    // (a rectangular operator, arpack_hip_csr_create_rect, is refused -- inside
-    // the agreement, so every rank leaves together)
-    if (!dist_all_ok(c, !A->rect && ahip_csr_col_span(A, &cmin, &cmax) == 0)) return -1;
+    // (a rectangular operator, arpack_hip_csr_create_rect, and an fp32 one,
+    // arpack_hip_csr_create_f32, are refused -- inside the agreement, so every
+    // rank leaves together)
+    if (!dist_all_ok(c, !A->rect && A->A.prec != 's' && ahip_csr_col_span(A, &cmin, &cmax) == 0))
+        return -1;
     if (cmax < 0) cmin = cmax = row0;  // empty operator block
     // share [row0, nloc, cmin, cmax] of every rank (allreduce of a one-hot table)
     std::vector<double> tab(4 * (size_t)P, 0.0);

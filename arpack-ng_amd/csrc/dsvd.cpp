@@ -59,6 +59,7 @@ int dsvd_create(DSvd& S, const arpack_hip_csr* A, int form) {
     S = DSvd{};
     if (!A || form < kSvdAuto || form > kSvdFused) return -1;
     const Csr& M = *ahip_csr_view(A);
+    if (M.prec == 's') return -1;  // an fp32 operator: the normal operator is fp64
     const int64_t m = M.n, n = ahip_csr_ncols(A), nnz = M.nnz;
     if (m < 1 || n < 1 || m > (int64_t)INT32_MAX || n > (int64_t)INT32_MAX) return -1;
     const int64_t k = m < n ? m : n, rows = m < n ? n : m;

@@ -96,6 +96,46 @@ static int ns_eupd(bool rvec, char howmny, int* select_out, R* dr_out, R* di_out
     std::vector<int> sel(ncv, 0);
     std::vector<double> Qh, M2;  // explicit Householder products for the device GEMMs
     if (rvec) {
+        if constexpr (kShadow) {
+            // `select` below marks POSITIONS on the diagonal of the Schur form
+            // computed here, by the index each Ritz value had when snaupd saved it
+            // (irr, iri, ibd) -- the order ITS Schur form gave.  The reference's
+            // float build computes both from one H, so the orders agree by
+            // construction; here snaupd worked on the fp64 shadow of H and this
+            // routine sees H as the caller's float workl holds it, and that
+            // rounding can change the order in which lahqr deflates (a wanted
+            // Ritz value was then replaced by an unwanted one).  So the saved
+            // values are first brought into the order of this H's Schur form:
+            // the same lahqr call as below on a copy, each diagonal position
+            // matched to the nearest saved value not yet taken.  Orders that
+            // agree (the usual case) leave everything as it was.
+            std::vector<double> Hc(workl + ih, workl + ih + (size_t)ldh * ncv), Zc((size_t)ldq * ncv, 0.0),
+                er(ncv), ei(ncv), nr(ncv), ni(ncv), nb(ncv);
+            for (int j = 0; j < ncv; ++j) Zc[j + (size_t)j * ldq] = 1.0;
+            if (la::lahqr(true, true, ncv, 1, ncv, Hc.data(), ldh, er.data(), ei.data(), 1, ncv,
+                          Zc.data(), ldq) != 0)
+                return -8;
+            std::vector<char> taken(ncv, 0);
+            for (int p = 0; p < ncv; ++p) {
+                int best = -1;
+                double bd = 0.0;
+                for (int q = 0; q < ncv; ++q) {
+                    if (taken[q]) continue;
+                    const double dist = la::lapy2(er[p] - workl[irr + q], ei[p] - workl[iri + q]);
+                    if (best < 0 || dist < bd) {
+                        best = q;
+                        bd = dist;
+                    }
+                }
+                taken[best] = 1;
+                nr[p] = workl[irr + best];
+                ni[p] = workl[iri + best];
+                nb[p] = workl[ibd + best];
+            }
+            std::memcpy(workl + irr, nr.data(), sizeof(double) * ncv);
+            std::memcpy(workl + iri, ni.data(), sizeof(double) * ncv);
+            std::memcpy(workl + ibd, nb.data(), sizeof(double) * ncv);
+        }
         bool reord = false;
         for (int j = 0; j < ncv; ++j) workl[ibounds + j] = j + 1;
         int np = ncv - nev, kev = nev;

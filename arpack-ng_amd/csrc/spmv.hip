@@ -487,6 +487,115 @@ __global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_eu(8))
                                           rng, fa);
 }
 
+// The fp32 operator's SELL-64 kernel (arpack_hip_csr_create_f32): csr_sell_body
+// without the FIN variants over the same slice and window tables -- XCD block
+// order, non-temporal value / column loads, double-buffered chunks of U column
+// steps, single- and multi-range (MR) windows.  An entry is a float value and
+// the 16-bit window column (6 B); x is float and its window is staged into LDS
+// as float (40 KB for the 10,240-column window, half the fp64 kernel's).  Each
+// row is summed in fp64 in column order and rounded once on the store:
+//   y_i = fl32(((0 + (double)a_i1 (double)x_1) + (double)a_i2 (double)x_2) + ...)
+// -- a product of two floats is exact in fp64, so y is bitwise SciPy's
+// (A32.astype(f64) @ x.astype(f64)).astype(f32), the OP of the s* fixtures.
+// waves_per_eu(8): at most 64 VGPRs, so two workgroups share a CU (32 waves).
+template <int U, bool MR>
+__global__ __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_csr_sell_f32(
+    const int64_t* __restrict__ sb_slice0, const int64_t* __restrict__ sptr,
+    const int32_t* __restrict__ srow, const int64_t* __restrict__ sb_c0,
+    const int32_t* __restrict__ sb_span, const uint16_t* __restrict__ scolw,
+    const float* __restrict__ sval, const float* __restrict__ x, float* __restrict__ y,
+    const int64_t* __restrict__ rng) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float ldsf[];
+    float* xw = ldsf;
+    constexpr int NW = kWinThreads / 64;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t sb = xcd_block(blockIdx.x, gridDim.x);
+    const int64_t c0 = sb_c0[sb];
+    const int span = sb_span[sb];
+    const int64_t s0 = sb_slice0[sb], s1 = sb_slice0[sb + 1];
+    struct Chunk {
+        float v[U];
+        int c[U];
+    };
+    auto load = [&](Chunk& ch, int64_t base, int w, int k0) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const bool in = k0 + u < w;
+            ch.v[u] = in ? ld<float, true>(sval + base + (int64_t)(k0 + u) * 64 + lane) : 0.0f;
+            ch.c[u] = in ? (int)ld<uint16_t, true>(scolw + base + (int64_t)(k0 + u) * 64 + lane) : 0;
+        }
+    };
+    int64_t s = s0 + wave;
+    int64_t base = 0;
+    int w = 0;
+    Chunk cur, nxt;
+    if (s < s1) {
+        base = sptr[s];
+        w = (int)((sptr[s + 1] - base) >> 6);
+        load(cur, base, w, 0);
+    }
+    if constexpr (MR) {
+#pragma unroll
+        for (int r = 0; r < kMaxRanges; ++r) {
+            const int64_t a = rng[8 * sb + r], ol = rng[8 * sb + 4 + r];
+            const int off = (int)(ol >> 32), len = (int)(ol & 0xffffffff);
+            for (int i = t; i < len; i += kWinThreads) xw[off + i] = x[a + i];
+        }
+    } else {
+        for (int i = t; i < span; i += kWinThreads) xw[i] = x[c0 + i];
+    }
+    __syncthreads();
+    for (; s < s1; s += NW) {
+        const int row = srow[s * 64 + lane];
+        const int64_t sn = s + NW;
+        int64_t nbase = 0;
+        int nw = 0;
+        if (sn < s1) {
+            nbase = sptr[sn];
+            nw = (int)((sptr[sn + 1] - nbase) >> 6);
+        }
+        double acc = 0.0;
+        int k = 0;
+        do {
+            if (k + U < w) load(nxt, base, w, k + U);
+            else if (sn < s1) load(nxt, nbase, nw, 0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc += (double)cur.v[u] * (double)xw[cur.c[u]];
+            cur = nxt;
+            k += U;
+        } while (k < w);
+        if (row >= 0) y[row] = (float)acc;
+        base = nbase;
+        w = nw;
+    }
+}
+
+// The fp32 operator's fallback (rows no window plan accepts): k_csr_vector on
+// float values and vectors, G lanes a row, each lane's partial and the lane
+// tree summed in fp64 (a fixed order: reproducible run to run), one rounding
+// to fp32 on the store.
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_csr_vector_f32(int64_t n, const int64_t* __restrict__ rp,
+                                                           const int32_t* __restrict__ col,
+                                                           const float* __restrict__ val,
+                                                           const float* __restrict__ x,
+                                                           float* __restrict__ y) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % G;
+    const int64_t rows_per_block = kBlock / G;
+    const int64_t stride = (int64_t)gridDim.x * rows_per_block;
+    for (int64_t row = (int64_t)blockIdx.x * rows_per_block + threadIdx.x / G; row < n;
+         row += stride) {
+        const int64_t b = rp[row], e = rp[row + 1];
+        double s = 0.0;
+        for (int64_t k = b + lane; k < e; k += G) s += (double)val[k] * (double)x[col[k]];
+#pragma unroll
+        for (int off = G / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, G);
+        if (lane == 0) y[row] = (float)s;
+    }
+}
+
 // Two slices per wave at once (s and s + NW): twice the independent column
 // streams per wave, each double-buffered.
 template <int U, bool XCD>
@@ -574,10 +683,12 @@ __global__ __launch_bounds__(kWinThreads) void k_csr_sell2(
 }
 
 // fill the SELL arrays: one 64-thread block per slice, lane = row of the slice
+// (V = double, or float for an fp32 operator)
+template <class V>
 __global__ void k_sell_fill(const int64_t* __restrict__ sptr, const int32_t* __restrict__ srow,
                             const int64_t* __restrict__ rp, const uint16_t* __restrict__ colw,
-                            const double* __restrict__ val, uint16_t* __restrict__ scolw,
-                            double* __restrict__ sval) {
+                            const V* __restrict__ val, uint16_t* __restrict__ scolw,
+                            V* __restrict__ sval) {
     const int64_t s = blockIdx.x;
     const int lane = threadIdx.x;
     const int64_t base = sptr[s];
@@ -586,7 +697,7 @@ __global__ void k_sell_fill(const int64_t* __restrict__ sptr, const int32_t* __r
     const int64_t b = row >= 0 ? rp[row] : 0, len = row >= 0 ? rp[row + 1] - rp[row] : 0;
     for (int k = 0; k < w; ++k) {
         const bool in = k < len;
-        sval[base + (int64_t)k * 64 + lane] = in ? val[b + k] : 0.0;
+        sval[base + (int64_t)k * 64 + lane] = in ? val[b + k] : V(0);
         scolw[base + (int64_t)k * 64 + lane] = in ? colw[b + k] : (uint16_t)0;
     }
 }
@@ -991,8 +1102,10 @@ int csr_build_sell(Csr& A, void** owned) {
         sb_slice0.push_back((int64_t)sptr.size() - 1);
     }
     const int64_t ns = (int64_t)sptr.size() - 1, padded = sptr.back();
+    const bool f32 = A.prec == 's';  // float values: 6 B a stored entry
     const size_t b0 = sizeof(int64_t) * sb_slice0.size(), b1 = sizeof(int64_t) * sptr.size(),
-                 b2 = sizeof(int32_t) * srow.size(), bv = sizeof(double) * (size_t)(padded ? padded : 1),
+                 b2 = sizeof(int32_t) * srow.size(),
+                 bv = (f32 ? sizeof(float) : sizeof(double)) * (size_t)(padded ? padded : 1),
                  bc = sizeof(uint16_t) * (size_t)(padded ? padded : 1);
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     char* d = nullptr;
@@ -1006,14 +1119,19 @@ int csr_build_sell(Csr& A, void** owned) {
     auto* d0 = (int64_t*)take(b0);
     auto* d1 = (int64_t*)take(b1);
     auto* d2 = (int32_t*)take(b2);
-    auto* dv = (double*)take(bv);
+    char* dv = take(bv);
     auto* dc = (uint16_t*)take(bc);
     bool cp = hok(hipMemcpy(d0, sb_slice0.data(), b0, hipMemcpyHostToDevice)) &&
               hok(hipMemcpy(d1, sptr.data(), b1, hipMemcpyHostToDevice)) &&
               hok(hipMemcpy(d2, srow.data(), b2, hipMemcpyHostToDevice));
-    if (cp && ns > 0)
-        AHIP_LAUNCH(k_sell_fill, dim3((unsigned)ns), dim3(64), 0, nullptr, d1, d2, A.rowptr,
-                           A.w_colw, A.val, dc, dv);
+    if (cp && ns > 0) {
+        if (f32)
+            AHIP_LAUNCH(k_sell_fill<float>, dim3((unsigned)ns), dim3(64), 0, nullptr, d1, d2, A.rowptr,
+                        A.w_colw, A.valf, dc, (float*)dv);
+        else
+            AHIP_LAUNCH(k_sell_fill<double>, dim3((unsigned)ns), dim3(64), 0, nullptr, d1, d2, A.rowptr,
+                        A.w_colw, A.val, dc, (double*)dv);
+    }
     if (!cp || !hok(hipDeviceSynchronize())) {
         (void)hipFree(d);
         return -2;
@@ -1021,7 +1139,8 @@ int csr_build_sell(Csr& A, void** owned) {
     A.s_sb_slice0 = d0;
     A.s_ptr = d1;
     A.s_row = d2;
-    A.s_val = dv;
+    if (f32) A.s_valf = (const float*)dv;
+    else A.s_val = (const double*)dv;
     A.s_colw = dc;
     A.s_nslices = ns;
     A.s_padded = padded;
@@ -1063,6 +1182,11 @@ int csr_analyse(Csr& A, int tile, int64_t** rblk_dev) {
 double csr_bytes(const Csr& A) {
     // bytes the selected kernel must move: val + column index (+ rowptr, x, y);
     // SELL: 10 B per stored nonzero + the 4-B row map (padding not counted)
+    if (A.prec == 's') {  // csr_spmv_f32: float values, x and y; SELL: 6 B a stored entry
+        if (A.kernel == kCsrSell && A.s_valf)
+            return 6.0 * (double)A.nnz + 4.0 * (double)A.n + 8.0 * (double)A.n;
+        return 8.0 * (double)A.nnz + 8.0 * (double)(A.n + 1) + 8.0 * (double)A.n;
+    }
     if (csr_sym_det_fallback(A)) {  // the full-storage kernel csr_spmv runs instead
         Csr F = A;
         F.kernel = A.s_val ? kCsrSell : (A.rblk ? kCsrStream : kCsrVector);
@@ -1266,6 +1390,37 @@ void csr_spmv(hipStream_t s, const Csr& A, const double* x, double* y, FinQueue*
         case 16: AHIP_LAUNCH(k_csr_vector<16>, dim3(g), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, A.val, x, y); break;
         case 32: AHIP_LAUNCH(k_csr_vector<32>, dim3(g), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, A.val, x, y); break;
         default: AHIP_LAUNCH(k_csr_vector<64>, dim3(g), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, A.val, x, y); break;
+    }
+}
+
+void csr_spmv_f32(hipStream_t s, const Csr& A, const float* x, float* y) {
+    if (A.kernel == kCsrSell && A.s_valf) {
+        const size_t lds = sizeof(float) * kWinX;
+        auto go = [&](auto kern) {
+            AHIP_LAUNCH(kern, dim3((unsigned)A.w_nsb), dim3(kWinThreads), lds, s, A.s_sb_slice0, A.s_ptr,
+                        A.s_row, A.w_sb_c0, A.w_sb_span, A.s_colw, A.s_valf, x, y,
+                        (const int64_t*)A.w_rng);
+        };
+        // s_unroll: column steps a chunk (arpack_hip_csr_set_kernel(A, 11, 4 | 6); 8
+        // steps would need 66 VGPRs: one workgroup a CU instead of two)
+        if (A.w_rng) A.s_unroll == 4 ? go(k_csr_sell_f32<4, true>) : go(k_csr_sell_f32<6, true>);
+        else A.s_unroll == 4 ? go(k_csr_sell_f32<4, false>) : go(k_csr_sell_f32<6, false>);
+        return;
+    }
+    const int G = A.group;
+    const int rows_per_block = kBlock / G;
+    int64_t g = (A.n + rows_per_block - 1) / rows_per_block;
+    if (g > 65536) g = 65536;
+    if (g < 1) g = 1;
+    auto go = [&](auto kern) {
+        AHIP_LAUNCH(kern, dim3((unsigned)g), dim3(kBlock), 0, s, A.n, A.rowptr, A.col, A.valf, x, y);
+    };
+    switch (G) {
+        case 4: go(k_csr_vector_f32<4>); break;
+        case 8: go(k_csr_vector_f32<8>); break;
+        case 16: go(k_csr_vector_f32<16>); break;
+        case 32: go(k_csr_vector_f32<32>); break;
+        default: go(k_csr_vector_f32<64>); break;
     }
 }
 

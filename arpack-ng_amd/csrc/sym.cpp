@@ -350,8 +350,10 @@ Task SolverT<R>::saitr(int k, int npk, int& iinfo) {
         const char* e = getenv("AHIP_CHAIN");
         return !(e && e[0] == '0');
     }();
-    // (not for the SVD's normal operator B'B: its steps stay the plain ones)
-    const bool chain_base = chain_env && free_run && bI && mode == 1 && ncv <= 64 && !svd;
+    // (not for the SVD's normal operator B'B, nor for the float family's free
+    // run on an fp32 operator: their steps stay the plain ones)
+    const bool chain_base = chain_env && free_run && bI && mode == 1 && ncv <= 64 && !svd &&
+                            std::is_same_v<R, double>;
     const bool chain_ok = chain_base && !arnoldi;
     // Folded steps (on top of chaining; AHIP_FOLD=0 disables): step j-1's DGKS
     // sweep is not a pass of its own.  Its update pass leaves r (before the

@@ -288,6 +288,58 @@ void arpack_hip_dnaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* 
                                   int* iparam, int* ipntr, double* workd, double* workl,
                                   int lworkl, int* info);
 
+/* ---- fp32 device operator: the single-precision family's free run ------------- *
+ * A square CSR matrix whose values are stored as float (rowptr int64[n+1], col
+ * int32[nnz], val f32[nnz]; the pointer rules of arpack_hip_csr_create).  The
+ * SpMV plans are the fp64 operator's (they read indices only); the values are
+ * kept as float alone -- SELL-64 entries of 6 B, no fp64 copy stays resident.
+ * Every index is checked.  0; -1 for a bad argument, an index outside [0, n) or
+ * arrays that could not be placed in HBM; -2 if the plan analysis failed.
+ *
+ * The product (arpack_hip_csr_spmv_f32: x, y device float[n]) sums each row in
+ * fp64 and rounds once on the store.  Its SELL form (arpack_hip_csr_kernel = 11)
+ * sums in column order, so y is bitwise
+ *   (A32 converted to fp64) @ (x converted to fp64), rounded to fp32;
+ * the fallback for rows no window plan accepts (kernel 0) sums in a fixed
+ * lane-tree order: reproducible run to run, within rounding of the above.
+ * arpack_hip_csr_set_kernel accepts 0, and 11 where the SELL layout exists
+ * (tile 4 or 6: column steps per chunk); -1 for every other form.
+ *
+ * An fp32 operator serves arpack_hip_csr_spmv_f32 / _time_f32 / _download_f32
+ * and the s* free runs below (mode 1, bmat 'I', one GPU).  The fp64 entries
+ * refuse it before anything runs: arpack_hip_csr_spmv, _download,
+ * _set_symmetric, _set_sym_accumulator, arpack_hip_dist_create,
+ * arpack_hip_dshift_create, arpack_hip_dgen_create*, arpack_hip_dsvd_create
+ * return -1 (arpack_hip_csr_time -1.0), and the d* / p* solver entries end with
+ * ido = 99, info = -11.  Likewise arpack_hip_csr_spmv_f32 returns -1 and the s*
+ * free runs end with info = -11 for an fp64 operator.  arpack_hip_csr_info,
+ * _sell_info, _kernel and _shape serve either precision. */
+int arpack_hip_csr_create_f32(arpack_hip_csr** A, int64_t n, int64_t nnz, const int64_t* rowptr,
+                              const int32_t* col, const float* val);
+/* 'd' or 's': the precision of A's stored values (-1 for a null A). */
+int arpack_hip_csr_precision(const arpack_hip_csr* A);
+int arpack_hip_csr_spmv_f32(const arpack_hip_csr* A, const float* x, float* y);
+/* Average device time (ms, hipEvents) of `reps` back-to-back fp32 products;
+ * -1.0 for a bad argument. */
+double arpack_hip_csr_time_f32(const arpack_hip_csr* A, const float* x, float* y, int reps);
+int arpack_hip_csr_download_f32(const arpack_hip_csr* A, int64_t* rowptr, int32_t* col, float* val);
+/* ssaupd_c / ssaupd_ / snaupd_ with OP = A served on the GPU by the fp32
+ * product: the argument lists of arpack_hip_dsaupd_csr, _dsaupd_csr_cycles and
+ * _dnaupd_csr_cycles with float arrays and tol.  The n-length data and kernels
+ * are fp32, reductions and the ncv-sized host work fp64, as in ssaupd_c. */
+void arpack_hip_ssaupd_csr(const arpack_hip_csr* A, int* ido, char const* bmat, int n,
+                           char const* which, int nev, float tol, float* resid, int ncv, float* v,
+                           int ldv, int* iparam, int* ipntr, float* workd, float* workl, int lworkl,
+                           int* info);
+void arpack_hip_ssaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* ido,
+                                  char const* bmat, int n, char const* which, int nev, float* tol,
+                                  float* resid, int ncv, float* v, int ldv, int* iparam, int* ipntr,
+                                  float* workd, float* workl, int lworkl, int* info);
+void arpack_hip_snaupd_csr_cycles(const arpack_hip_csr* A, int max_cycles, int* ido,
+                                  char const* bmat, int n, char const* which, int nev, float* tol,
+                                  float* resid, int ncv, float* v, int ldv, int* iparam, int* ipntr,
+                                  float* workd, float* workl, int lworkl, int* info);
+
 /* ---- truncated SVD on the device (EXAMPLES/SVD/dsvd.f, SciPy's svds) ---------- *
  * A rectangular CSR matrix, nrows x ncols (the pointer rules of
  * arpack_hip_csr_create).  arpack_hip_csr_spmv reads x of ncols and writes y of
